@@ -8,6 +8,12 @@ A "step" is one `HWWithStyleTrainer._train_iteration` (one lesson of the 7-lesso
 on one rank's synthetic author batch; steps are timed in whole curriculum cycles where possible. Data parallel runs give every rank
 its own author shard (weak scaling) and all-reduce the gradient sets over RCCL; `value` = N*K / max-over-ranks elapsed time.
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the line. `--full` adds, after the timed steps, everything else the line can
+carry (whole-cycle rate, roofline profile, dead-gradient elimination, generation rate, CPU baseline, the other BASELINE workloads, clocks,
+RCCL's init report); those keys are null in a plain run. `--dump-outputs DIR` writes what the last timed step computed (its logged losses
+and the weights it left) as DIR/<name>.npy. The number and order of the steps before it depend on the arguments alone (a fixed recorder
+warm-up, a start phase from a fixed cost model), so two builds run with the same arguments compare output for output.
 """
 import argparse
 import json
@@ -41,6 +47,35 @@ WORKLOADS = {
 }
 PEAK_FP32_MFMA_TFLOPS = 157.3  # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32 at 256 CU x 2.4 GHz
 LESSONS = ("count", "gen", "auto", "disc", "gen", "auto", "disc")   # the shipped GAN curriculum
+# GPU ms per lesson kind of the default workload (round-6 bench lines, profiles/r06_bench_boxes.txt). The timed window's start phase is chosen
+# from this fixed model rather than from this run's timings, so that the steps a run takes depend on its arguments alone. It is applied to every
+# GAN workload: for K % 7 != 0 on the RIMES or one-line workloads the phase may differ from the one their own lesson costs would pick (for K a
+# multiple of 7 every phase has the same lesson mix and phase 0 is taken).
+LESSON_MS = {"count": 7.6, "gen": 7.7, "auto": 22.9, "disc": 4.4}
+# --dump-outputs: at most 2M weights (8 MB) per sub-network, a fixed seeded sample beyond that, and fewer per network where the model has so
+# many sub-networks that the weights would pass DUMP_MAX_BYTES (the logged scalars add a few hundred bytes)
+DUMP_SAMPLE, DUMP_SEED, DUMP_MAX_BYTES = 1 << 21, 2024, 60 << 20
+
+
+def dump_outputs(path, model, log):
+    """what the last timed step computed, as path/<name>.npy: its logged values (log_<key>, float64) and, per sub-network, the weights and
+    float buffers it left (weights_<net>, float32, state_dict order; a fixed seeded sample of DUMP_SAMPLE values where the network holds more,
+    fewer where DUMP_MAX_BYTES would be passed)"""
+    import re
+    os.makedirs(path, exist_ok=True)
+    for k, v in log.items():
+        np.save(os.path.join(path, "log_%s.npy" % re.sub(r"[^\w.-]", "_", k)), np.asarray(v, dtype=np.float64))
+    nets = {}
+    for name, t in model.state_dict().items():
+        if t.is_floating_point():
+            nets.setdefault(name.split(".")[0], []).append(t.detach().reshape(-1))
+    limit = min(DUMP_SAMPLE, DUMP_MAX_BYTES // 4 // max(len(nets), 1))
+    for net, ts in nets.items():
+        flat = torch.cat(ts)
+        if flat.numel() > limit:
+            idx = torch.randint(0, flat.numel(), (limit,), generator=torch.Generator().manual_seed(DUMP_SEED)).sort().values
+            flat = flat[idx.to(flat.device)]
+        np.save(os.path.join(path, "weights_%s.npy" % net), flat.float().cpu().numpy())
 
 
 def peaked_offset_fn(num_class, seed=5, blank_frac=0.7, gain=10.0):
@@ -194,6 +229,10 @@ def main():
     ap.add_argument("--no-other-workloads", action="store_true",
                     help="skip the short child-process runs of the other BASELINE configs (iam_auto_b28_w512, iam_gan_b1a1_w512, rimes_gan_b4a2_w256_1024) "
                          "that follow the timed region of the default workload")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the secondary measurements (whole cycles, roofline, dead-gradient elimination, gen lines/s, "
+                         "CPU baseline, other workloads, clocks, RCCL report); a plain run reports the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's logged losses and the weights it left as DIR/<name>.npy")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -211,7 +250,7 @@ def main():
     rccl_log = None
     if world > 1 or force_dp:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1"); os.environ.setdefault("MASTER_PORT", "29533")
-        if backend == "nccl" and "NCCL_DEBUG" not in os.environ:
+        if backend == "nccl" and "NCCL_DEBUG" not in os.environ and args.full:
             # self-diagnosing multi-GPU runs: RCCL's init / topology report goes to a per-rank file (stdout must stay one JSON line) and
             # rank 0 folds its summary (ranks, channels, transports) into the JSON's data_parallel.rccl
             import tempfile
@@ -233,7 +272,7 @@ def main():
     # The contract: W untimed warm-up steps, then EXACTLY K timed steps - `steps` / `warmup` in the JSON are the driver's numbers. The curriculum
     # is a 7-lesson cycle whose lessons differ 6x in cost (auto 25 ms, disc 4.5 ms), and the launch-list recorder (replay.py) needs its
     # sightings before the step rate is the product's steady state; both are dealt with BEFORE the counted warm-up, in a recorder warm-up whose
-    # length is reported (`recorder_warmup_steps`): whole cycles until the recorder is quiet, plus 0-6 lessons that put the K-step window at
+    # length is reported (`recorder_warmup_steps`): a fixed number of whole cycles, plus 0-6 lessons that put the K-step window at
     # the curriculum phase whose lesson mix is closest to the cycle's mean cost (`timed_window`; irrelevant when K is a multiple of 7).
     steps_req, warm_req = args.steps, args.warmup
     args.warmup = max(args.warmup, 0)
@@ -297,19 +336,21 @@ def main():
     trainer._side_wgrad = side_wgrad
     ops.SIDE_WGRAD = side_wgrad is True
 
-    # Recorder warm-up (before the counted warm-up, not part of `warmup`): whole cycles for at least WARM_SECONDS of wall time (clock / power
-    # state) and until the launch-list recorder (replay.py) has gone quiet: a pass is recorded at its 3rd / 24th sighting (a one-off eager run
-    # of every backward variant plus a self-check, 20-50 ms), i.e. around cycle 12 for the recogniser on generated lines. Warm until no program
-    # has been recorded for QUIET_CYCLES cycles, at least REPLAY_MIN_CYCLES and at most 40 cycles. `recorder_warmup_steps` reports its length.
-    WARM_SECONDS = 1.5
+    # Recorder warm-up (before the counted warm-up, not part of `warmup`; clock / power state, plans, workspaces, and the launch-list recorder
+    # (replay.py): a pass is recorded at its 3rd / 24th sighting - a one-off eager run of every backward variant plus a self-check, 20-50 ms -
+    # which the recogniser on generated lines reaches around cycle 12). Its length is a fixed number of steps, 40 whole cycles of the GAN
+    # curriculum (3-5 s) or 100 steps of a one-lesson trainer: a length that ended when the recorder went quiet would depend on the build (the
+    # geometries it sees come from the spacer's numerics, a program can fail its self-check), and every step before the timed window must
+    # depend on the arguments alone for --dump-outputs to compare two builds. `recorder_warmup_steps` reports the length; `recorder` reports
+    # where the recorder made its last program and whether it was quiet for the last QUIET_CYCLES cycles of the warm-up.
+    PRE_STEPS = 40 * cycle if gan else 100
+    QUIET_CYCLES, REPLAY_MIN_CYCLES = 4, 14      # (REPLAY_MIN_CYCLES: the --full dead-gradient run's own settling)
     it = 0
     barrier()
-    tw = time.perf_counter()
     pre_done = 0
-    QUIET_CYCLES, REPLAY_MIN_CYCLES = 4, 14
-    quiet, recorded = 0, -1
+    recorded, last_record_at = _replay.STATS["captures"] + _replay.STATS["rejected"], 0
     pre_marks = None
-    while True:
+    while pre_done < PRE_STEPS:
         last = [torch.cuda.Event(enable_timing=True) for _ in range(cycle + 1)]
         for k in range(cycle):
             last[k].record()
@@ -318,17 +359,16 @@ def main():
         pre_marks = last
         pre_done += cycle
         now = _replay.STATS["captures"] + _replay.STATS["rejected"]
-        quiet, recorded = (quiet + 1 if now == recorded else 0), now
-        torch.cuda.synchronize()
-        settled = (not _replay.ENABLED) or not gan or (quiet >= QUIET_CYCLES and pre_done >= REPLAY_MIN_CYCLES * cycle) or pre_done >= 40 * cycle
-        waiting = 0.0 if (time.perf_counter() - tw >= WARM_SECONDS and settled) else 1.0
-        if agree_max(waiting) == 0.0 or pre_done >= 100 * cycle:
-            break
+        if now != recorded:
+            recorded, last_record_at = now, pre_done
+    torch.cuda.synchronize()
+    recorder = {"last_program_after_steps": last_record_at, "quiet_for_last_cycles": pre_done - last_record_at >= QUIET_CYCLES * cycle}
     # phase of the timed window: with K not a multiple of the cycle the window's lesson mix depends on where it starts; pick the start whose
-    # mix costs closest to K x the cycle's mean (lesson costs = GPU time between step starts in the last recorder warm-up cycle)
+    # mix costs closest to K x the cycle's mean (lesson costs from LESSON_MS for every GAN workload, so the phase is a function of K alone;
+    # the reported ratio uses this run's GPU time between step starts in the last recorder warm-up cycle)
     timed_window = None
     if cycle > 1:
-        cost = [pre_marks[k].elapsed_time(pre_marks[k + 1]) for k in range(cycle)]       # index = lesson (the loop above runs whole cycles from lesson 0)
+        cost = [LESSON_MS[name] for name in LESSONS]
         mean = sum(cost) / cycle
         best, best_err = 0, None
         for s0 in range(cycle):
@@ -340,8 +380,11 @@ def main():
         for _ in range(extra):
             trainer._train_iteration(it); it += 1
         pre_done += extra
-        timed_window = {"first_lesson": "%d:%s" % (best, LESSONS[best]), "lesson_mix_cost_vs_cycle_mean": round(1.0 + (sum(cost[(best + k) % cycle] for k in range(args.steps)) - args.steps * mean) / (args.steps * mean), 4),
-                        "how": "start phase of the K timed steps chosen before the counted warm-up so that the window's lesson mix costs closest to K x the cycle mean (exact when K % 7 == 0)"}
+        measured = [pre_marks[k].elapsed_time(pre_marks[k + 1]) for k in range(cycle)]   # index = lesson (the loop above runs whole cycles from lesson 0)
+        mmean = sum(measured) / cycle
+        timed_window = {"first_lesson": "%d:%s" % (best, LESSONS[best]), "lesson_mix_cost_vs_cycle_mean": round(1.0 + (sum(measured[(best + k) % cycle] for k in range(args.steps)) - args.steps * mmean) / (args.steps * mmean), 4),
+                        "how": "start phase of the K timed steps chosen before the counted warm-up so that the window's lesson mix costs closest to K x the cycle mean "
+                               "under bench.py's fixed per-lesson cost model (exact when K % 7 == 0); the ratio is from this run's lesson times"}
     # the counted warm-up: exactly W untimed steps
     for _ in range(args.warmup):
         trainer._train_iteration(it); it += 1
@@ -352,25 +395,28 @@ def main():
     flat_params.COMM.update(collectives=0, bytes=0)
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]   # per-lesson GPU time: one event between steps
     first_lesson = it % cycle
-    clocks = ClockSampler(local)
-    clocks.start()
+    clocks = ClockSampler(local) if args.full else None
+    if clocks is not None:
+        clocks.start()
     barrier()
     t0 = time.perf_counter()
     for k in range(args.steps):
         marks[k].record()
-        trainer._train_iteration(it); it += 1
+        log = trainer._train_iteration(it); it += 1
     marks[args.steps].record()
-    trainer.flush_log()
+    log = trainer.flush_log() or log     # the newest log: the last step's (a pipelined log returns an earlier step's from _train_iteration)
     barrier()
     elapsed = time.perf_counter() - t0
-    clock_report = clocks.stop()
+    clock_report = clocks.stop() if clocks is not None else None
     st = dict(CharStyleEncoder.stats)
     comm = dict(flat_params.COMM)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trainer.model, log)
 
     # Secondary: whole curriculum cycles (>= 10 cycles and >= 1.5 s) right after the timed region - the figure earlier rounds reported as `value`
     # when they rounded the driver's K up to whole cycles; kept so that a K that is not a multiple of 7 can be compared with the cycle average
     whole = None
-    if gan:
+    if gan and args.full:
         n_w = int(agree_max(float(max(10 * cycle, int(1.5 / max(elapsed / args.steps, 1e-6)) // cycle * cycle + cycle))))
         n_w = min(n_w, 2100)
         barrier()
@@ -386,12 +432,12 @@ def main():
     # Roofline measurement, AFTER the timed region (round 3 profiled cycles inside it: `value` carried the event packets and the
     # side-stream-off mode on a third of the driver's steps). The library records every MFMA launch's own begin / end timestamps
     # (hwg_prof_*); the weight-gradient side stream is off here because co-running kernels inflate each other's durations.
-    profiling = rank == 0 and not os.environ.get("HWG_BENCH_NO_PROF")
+    profiling = args.full and rank == 0 and not os.environ.get("HWG_BENCH_NO_PROF")
     PROF_CYCLES = int(os.environ.get("HWG_BENCH_PROF_CYCLES", "2"))
     prof_steps = 0
     prof_elapsed = 0.0
     if world > 1:
-        profiling_any = True   # every rank runs the same lessons (collectives inside); only rank 0 records
+        profiling_any = args.full   # every rank runs the same lessons (collectives inside); only rank 0 records
     else:
         profiling_any = profiling
     prof = []
@@ -424,7 +470,7 @@ def main():
     # no weight-gradient kernels for the frozen recogniser and for the discriminator outside disc lessons - SURVEY 8d's "minimum necessary"
     # variant; weights and losses are bit-identical, tests/test_trainer_gpu.py). `value` itself is the reference's launches, as executed.
     min_nec = None
-    if gan and not os.environ.get("HWG_BENCH_NO_MINNEC"):
+    if gan and args.full and not os.environ.get("HWG_BENCH_NO_MINNEC"):
         trainer.skip_unused_grads = True
         n2 = 3 * cycle
         # untimed: switch the gradient requirements / plans over and let the launch-list recorder settle again - the recogniser's backward passes
@@ -463,7 +509,7 @@ def main():
     # secondary metric of BASELINE.json ("and gen lines/sec"): HWWithStyle.forward(label, lengths, style) -> images, inference only,
     # measured AFTER the timed training region on the same weights (spacer -> host insert_spaces -> generator; one line = 64 x ~4T px)
     gen = None
-    if rank == 0 and not args.no_gen:
+    if rank == 0 and args.full and not args.no_gen:
         model = trainer.model
         model.eval()
         B = 64            # a generation service batches requests; the training batch (8 lines) is launch-bound at 1.6 ms per call
@@ -497,7 +543,7 @@ def main():
             f[0] += flops; f[1] += dt; f[2] += 1
             g = by_shape.setdefault((kind, shape), [0.0, 0.0, 0])
             g[0] += flops; g[1] += dt; g[2] += 1
-        if os.environ.get("HWG_CONV_DUMP"):
+        if args.full and os.environ.get("HWG_CONV_DUMP"):
             with open(os.environ["HWG_CONV_DUMP"], "w") as fh:
                 fh.write("# per-shape MFMA conv launches in the profiled cycles after the timed region (%d steps): time_ms  launches  avg_us  TFLOP/s  kind  shape(N,H,W,C,K,R,S,stride,pad,dil,mode,network)  work (FLOPs; bytes for the reduce kinds)\n" % prof_steps)
                 for (kind, shape), (fl, sec, n) in sorted(by_shape.items(), key=lambda kv: -kv[1][1]):
@@ -596,7 +642,7 @@ def main():
             except (OSError, KeyError, ValueError):
                 pass
         cpu = None
-        if world == 1 and not args.no_cpu_baseline and gan:
+        if world == 1 and args.full and not args.no_cpu_baseline and gan:
             # the oracle's CPU cycle runs in a child process (it never touches the GPU) under a hard timeout
             import subprocess
             B = wl["batch_size"] * wl["a_batch_size"]
@@ -618,7 +664,7 @@ def main():
         # exec of a process that has touched the GPU; the parent's few GB stay resident next to it): driver-visible numbers for configs[1],
         # [2] and [4] instead of builder-only ones. Fixed budget: 42 / 60 timed steps each, no CPU baseline, no generation figure.
         others = None
-        if world == 1 and args.workload == "iam_gan_b4a2_w512" and not args.no_other_workloads and not os.environ.get("HWG_BENCH_NO_OTHERS"):
+        if world == 1 and args.full and args.workload == "iam_gan_b4a2_w512" and not args.no_other_workloads and not os.environ.get("HWG_BENCH_NO_OTHERS"):
             import subprocess
             others = {}
             for wname, k_steps in (("iam_auto_b28_w512", 60), ("iam_gan_b1a1_w512", 42), ("rimes_gan_b4a2_w256_1024", 42)):
@@ -627,7 +673,7 @@ def main():
                 t_child = time.perf_counter()
                 try:
                     r = subprocess.run([sys.executable, os.path.abspath(__file__), "--workload", wname, "--steps", str(k_steps), "--warmup", "7", "--no-cpu-baseline",
-                                        "--no-gen", "--no-other-workloads"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=240.0)
+                                        "--no-gen", "--no-other-workloads", "--full"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=240.0)
                     j = json.loads(r.stdout.strip().splitlines()[-1])
                     rl = j.get("roofline") or {}
                     others[wname] = {"metric": j["metric"], "value": j["value"], "unit": j["unit"], "ms_per_step": j["ms_per_step"], "steps": j["steps"], "warmup": j["warmup"],
@@ -640,7 +686,7 @@ def main():
         out = {
             "metric": "G+D train steps/sec" if gan else "AE train steps/sec", "value": round(world * args.steps / elapsed, 4), "unit": "steps/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "steps_requested": steps_req, "warmup_requested": warm_req,
-            "recorder_warmup_steps": pre_done, "timed_window": timed_window, "whole_cycles": whole, "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True,
+            "recorder_warmup_steps": pre_done, "recorder": recorder, "timed_window": timed_window, "whole_cycles": whole, "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": args.workload, "config_file": cfg["name"], "lines_per_gpu_step": wl["batch_size"] * wl["a_batch_size"],
                        "authors_per_gpu": wl["batch_size"], "a_batch_size": wl["a_batch_size"], "line_px": "64x%d" % wl["width"],

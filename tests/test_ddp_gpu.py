@@ -294,11 +294,10 @@ def test_single_rank_rccl_exchange_is_the_identity(cuda, tmp_path):
         assert torch.equal(v, forced["params"][k]), "%s differs after a cycle with the one-rank RCCL exchange" % k
 
 
-def test_bench_rank_sharded_path_with_two_gloo_ranks(cuda, tmp_path):
-    """`bench.py --gpus 2` as the driver launches it (one process per rank, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment),
-    here with HWG_DIST_BACKEND=gloo so that both ranks can share the one GPU of the lease: the rank-sharded path (per-rank author shards,
-    gradient-set all-reduces, max-over-ranks timing, rank 0's JSON line) must run and report a 2-rank job. Keeps SURVEY 8(e)'s N > 1 bench
-    path from rotting while no multi-GPU node is available to the build."""
+def _bench_two_gloo_ranks(tmp_path, *extra):
+    """`bench.py --gpus 2 --steps 7 --warmup 0` as the driver launches it (one process per rank, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from
+    the environment), here with HWG_DIST_BACKEND=gloo so that both ranks can share the one GPU of the lease; returns rank 0's JSON line after
+    checking that the rank-sharded path (per-rank author shards, gradient-set all-reduces, max-over-ranks timing) reported a 2-rank job"""
     import json
     import subprocess
     import sys
@@ -308,7 +307,8 @@ def test_bench_rank_sharded_path_with_two_gloo_ranks(cuda, tmp_path):
     for r in range(2):
         env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE="2", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), HWG_DIST_BACKEND="gloo",
                    HWG_BENCH_NO_MINNEC="1", HWG_BENCH_PROF_CYCLES="1")
-        procs.append(subprocess.Popen([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "7", "--warmup", "0", "--no-cpu-baseline", "--no-gen"],
+        procs.append(subprocess.Popen([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "7", "--warmup", "0", "--no-cpu-baseline", "--no-gen",
+                                       *extra],
                                       cwd=str(tmp_path), env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     outs = [p.communicate(timeout=900) for p in procs]
     for p, (so, se) in zip(procs, outs):
@@ -321,4 +321,20 @@ def test_bench_rank_sharded_path_with_two_gloo_ranks(cuda, tmp_path):
     assert line["data_parallel"]["collectives_per_step"] > 0 and line["data_parallel"]["allreduce_mbytes_per_step"] > 0
     assert line["value"] > 0 and line["value"] == line["value"] and line["value"] != float("inf")
     assert abs(line["value"] - 2 * 7 / (line["ms_per_step"] * 7e-3)) < 0.01 * line["value"]      # whole-job aggregate: N x K / max-over-ranks time
+    return line
+
+
+def test_bench_rank_sharded_path_with_two_gloo_ranks(cuda, tmp_path):
+    """`bench.py --gpus 2 --full` with two gloo ranks on the one GPU: the rank-sharded path and the secondary loops after the timed region that
+    every rank runs (whole cycles with their max-over-ranks timing, the profiled cycles with collectives inside) must run and report a 2-rank
+    job. Keeps SURVEY 8(e)'s N > 1 bench path from rotting while no multi-GPU node is available to the build."""
+    line = _bench_two_gloo_ranks(tmp_path, "--full")
     assert line["other_workloads"] is None
+
+
+def test_bench_plain_run_with_two_gloo_ranks(cuda, tmp_path):
+    """`bench.py --gpus 2` without --full, the driver's launch: the same 2-rank job, and none of the secondary measurements ran"""
+    line = _bench_two_gloo_ranks(tmp_path)
+    for key in ("whole_cycles", "roofline", "gen_lines_per_sec", "cpu_baseline", "minimum_necessary", "other_workloads", "clocks"):
+        assert line[key] is None, key
+    assert line["data_parallel"]["rccl"] is None

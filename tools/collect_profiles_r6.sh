@@ -7,21 +7,21 @@ OUT=$GRAFT_REPO_ROOT/gpurun_out/r6prof
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 STEPS="--steps 28 --warmup 7"
-HWG_CONV_DUMP=$OUT/conv_shapes.txt timeout 600 python bench.py --steps 20 --warmup 5 > $OUT/bench_line.json 2> $OUT/bench_err.log
+HWG_CONV_DUMP=$OUT/conv_shapes.txt timeout 600 python bench.py --full --steps 20 --warmup 5 > $OUT/bench_line.json 2> $OUT/bench_err.log
 python tools/prof_summary.py gd $OUT/conv_shapes.txt > $OUT/gd_recomputed.txt 2>&1
-timeout 600 python bench.py --steps 140 --warmup 14 --no-cpu-baseline --no-other-workloads > $OUT/bench_line_long.json 2>> $OUT/bench_err.log
-HWG_BENCH_NO_MINNEC=1 HWG_CONV_DUMP=$OUT/conv_shapes_under_tracer.txt timeout 400 rocprofv3 --kernel-trace --stats -d $OUT/kt -o kt -f csv -- python3 bench.py $STEPS --no-cpu-baseline --no-gen --no-other-workloads > $OUT/kt.log 2>&1
+timeout 600 python bench.py --full --steps 140 --warmup 14 --no-cpu-baseline --no-other-workloads > $OUT/bench_line_long.json 2>> $OUT/bench_err.log
+HWG_BENCH_NO_MINNEC=1 HWG_CONV_DUMP=$OUT/conv_shapes_under_tracer.txt timeout 400 rocprofv3 --kernel-trace --stats -d $OUT/kt -o kt -f csv -- python3 bench.py --full $STEPS --no-cpu-baseline --no-gen --no-other-workloads > $OUT/kt.log 2>&1
 cp $OUT/kt/*kernel_stats.csv $OUT/kernel_stats_b4a2_w512.csv 2>/dev/null || find $OUT/kt -name "*kernel_stats.csv" -exec cp {} $OUT/kernel_stats_b4a2_w512.csv \;
 python tools/launch_census.py $OUT/kernel_stats_b4a2_w512.csv $OUT/kt.log > $OUT/launch_census.txt 2>&1
 KT=$(find $OUT/kt -name "*kernel_trace.csv" | head -1)
 [ -n "$KT" ] && python tools/kernel_by_grid.py $KT 300 > $OUT/kernel_by_grid.txt 2>&1
 for c in FETCH_SIZE WRITE_SIZE "SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE"; do
   tag=$(echo $c | cut -d' ' -f1)
-  HWG_BENCH_NO_MINNEC=1 timeout 400 rocprofv3 --kernel-trace --pmc $c -d $OUT/pmc_$tag -o p -- python3 bench.py --steps 7 --warmup 7 --no-cpu-baseline --no-gen --no-other-workloads > $OUT/pmc_$tag.log 2>&1
+  HWG_BENCH_NO_MINNEC=1 timeout 400 rocprofv3 --kernel-trace --pmc $c -d $OUT/pmc_$tag -o p -- python3 bench.py --full --steps 7 --warmup 7 --no-cpu-baseline --no-gen --no-other-workloads > $OUT/pmc_$tag.log 2>&1
 done
 for c in "SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS" "SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_INSTS_VALU"; do
   tag=$(echo $c | cut -d' ' -f1)
-  HWG_BENCH_NO_MINNEC=1 timeout 400 rocprofv3 --kernel-trace --pmc $c -d $OUT/pmc_$tag -o p -- python3 bench.py --steps 7 --warmup 7 --no-cpu-baseline --no-gen --no-other-workloads > $OUT/pmc_$tag.log 2>&1
+  HWG_BENCH_NO_MINNEC=1 timeout 400 rocprofv3 --kernel-trace --pmc $c -d $OUT/pmc_$tag -o p -- python3 bench.py --full --steps 7 --warmup 7 --no-cpu-baseline --no-gen --no-other-workloads > $OUT/pmc_$tag.log 2>&1
 done
 python tools/pmc_probe.py $(find $OUT/pmc_SQ_INSTS_LDS $OUT/pmc_SQ_BUSY_CYCLES -name "*.db") > $OUT/sq_counters.txt 2>&1
 rm -rf $OUT/pmc_SQ_INSTS_LDS $OUT/pmc_SQ_BUSY_CYCLES
@@ -42,8 +42,8 @@ timeout 400 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/shapes/write -o sw
 python tools/pmc_shapes.py parse $OUT/conv_shapes.txt $OUT/shapes $OUT/pmc_shapes.json > $OUT/shapes_parse.log 2>&1
 rm -rf $OUT/shapes
 for wl in iam_gan_b1a1_w512 rimes_gan_b4a2_w256_1024 iam_auto_b28_w512; do
-  timeout 400 python bench.py --workload $wl $STEPS --no-cpu-baseline --no-other-workloads > $OUT/bench_$wl.json 2> $OUT/bench_$wl.err
-  HWG_BENCH_NO_MINNEC=1 timeout 400 rocprofv3 --kernel-trace --stats -d $OUT/kt_$wl -o kt -f csv -- python3 bench.py --workload $wl --steps 14 --warmup 7 --no-cpu-baseline --no-gen --no-other-workloads > $OUT/kt_$wl.log 2>&1
+  timeout 400 python bench.py --full --workload $wl $STEPS --no-cpu-baseline --no-other-workloads > $OUT/bench_$wl.json 2> $OUT/bench_$wl.err
+  HWG_BENCH_NO_MINNEC=1 timeout 400 rocprofv3 --kernel-trace --stats -d $OUT/kt_$wl -o kt -f csv -- python3 bench.py --full --workload $wl --steps 14 --warmup 7 --no-cpu-baseline --no-gen --no-other-workloads > $OUT/kt_$wl.log 2>&1
   find $OUT/kt_$wl -name "*kernel_stats.csv" -exec cp {} $OUT/kernel_stats_$wl.csv \;
   rm -rf $OUT/kt_$wl
 done

@@ -3,7 +3,7 @@
 set -u
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/${1:-r6b}; rm -rf $O; mkdir -p $O
-timeout 900 python bench.py --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench_err.log
-timeout 600 python bench.py --steps 140 --warmup 14 --no-cpu-baseline --no-other-workloads > $O/bench_line_long.json 2>> $O/bench_err.log
-timeout 600 python bench.py > $O/bench_line_default.json 2>> $O/bench_err.log
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench_err.log
+timeout 600 python bench.py --full --steps 140 --warmup 14 --no-cpu-baseline --no-other-workloads > $O/bench_line_long.json 2>> $O/bench_err.log
+timeout 600 python bench.py --full > $O/bench_line_default.json 2>> $O/bench_err.log
 for f in $O/bench_line*.json; do grep '^{"metric"' $f | tail -1 | cut -c1-330; done

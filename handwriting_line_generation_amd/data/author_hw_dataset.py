@@ -331,7 +331,7 @@ class ShardedLoader:
         return len(self._batches())
 
     def _collate(self, items):
-        inst = collate(items)
+        inst = (getattr(self.dataset, "collate", None) or collate)(items)     # (HWDataset brings its own: one line per item)
         return pad_width(inst, self.width_bucket) if self.width_bucket else inst
 
     def __iter__(self):
@@ -344,24 +344,41 @@ DATASETS = {}
 
 
 def getDataLoader(config, split, rank=0, world=1):
-    """data_loader.getDataLoader of the reference (data_loader/data_loaders.py:11-75) for the author-grouped line datasets -> (train, valid).
-    `data_loader.width_bucket` (pixels, optional, not in the reference) switches width bucketing on, see ShardedLoader."""
+    """data_loader.getDataLoader of the reference (data_loader/data_loaders.py:11-75) for the line datasets -> (train, valid).
+    `data_loader.width_bucket` (pixels, optional, not in the reference) switches width bucketing on, see ShardedLoader.
+    An `augmentation` value the reference answers with Tensmeyer brightness + mesh warp (the two recogniser pre-training configs: true /
+    "warp") is executed on the GPU on the collated batch: the dataset is constructed un-augmented and its loader wrapped in
+    device_augment.DeviceAugment - per config, so the validation loader (which inherits `augmentation`, data_loaders.py:19-21) is wrapped
+    too. Every other value takes the path it always took."""
+    from .device_augment import DeviceAugment, device_variant
     dl = config["data_loader"]
     if not DATASETS:
         from .author_rimeslines_dataset import AuthorRIMESLinesDataset
-        DATASETS.update(AuthorHWDataset=AuthorHWDataset, AuthorRIMESLinesDataset=AuthorRIMESLinesDataset)
+        from .hw_dataset import HWDataset
+        DATASETS.update(AuthorHWDataset=AuthorHWDataset, AuthorRIMESLinesDataset=AuthorRIMESLinesDataset, HWDataset=HWDataset)
     if dl["data_set_name"] not in DATASETS:
-        raise NotImplementedError("dataset %r: only the author-grouped IAM / RIMES line datasets have a loader here" % dl["data_set_name"])
+        raise NotImplementedError("dataset %r: only the IAM line dataset and the author-grouped IAM / RIMES line datasets have a loader here" % dl["data_set_name"])
     cls = DATASETS[dl["data_set_name"]]
     val = dict(config.get("validation", {}))
     for k, v in dl.items():
         val.setdefault(k, v)
     wb = dl.get("width_bucket", 0)
+    device = torch.device("cuda", int(config.get("gpu", 0) or 0)) if config.get("cuda", True) else None
+
+    def build(part, cfg, *loader_args, **loader_kw):
+        variant = device_variant(dl["data_set_name"], cfg.get("augmentation"))
+        if variant is None:
+            return ShardedLoader(cls(dl["data_dir"], part, cfg), *loader_args, **loader_kw)
+        if device is None or not torch.cuda.is_available():      # there is no CPU execution of the brightness + warp augmentation
+            from .device_augment import REFUSAL
+            raise NotImplementedError(REFUSAL % (cfg.get("augmentation"),))
+        ds = cls(dl["data_dir"], part, dict(cfg, augmentation=None))
+        if not len(ds):
+            return ShardedLoader(ds, *loader_args, **loader_kw)
+        return DeviceAugment(ShardedLoader(ds, *loader_args, **loader_kw), variant, device, cfg.get("augmentation"))
+
     if split == "train":
-        train = cls(dl["data_dir"], "train", dl)
-        valid = cls(dl["data_dir"], "valid", val)
-        tl = ShardedLoader(train, dl["batch_size"], dl.get("shuffle", True), dl.get("num_workers", 1), rank, world, width_bucket=wb)
-        vl = ShardedLoader(valid, val.get("batch_size", dl["batch_size"]), val.get("shuffle", False), val.get("num_workers", 1), width_bucket=wb) if len(valid) else None
-        return tl, vl
-    test = cls(dl["data_dir"], split, val)
-    return ShardedLoader(test, val.get("batch_size", dl["batch_size"]), False, val.get("num_workers", 1), width_bucket=wb), None
+        tl = build("train", dl, dl["batch_size"], dl.get("shuffle", True), dl.get("num_workers", 1), rank, world, width_bucket=wb)
+        vl = build("valid", val, val.get("batch_size", dl["batch_size"]), val.get("shuffle", False), val.get("num_workers", 1), width_bucket=wb)
+        return tl, (vl if len(vl.dataset) else None)
+    return build(split, val, val.get("batch_size", dl["batch_size"]), False, val.get("num_workers", 1), width_bucket=wb), None

@@ -2245,6 +2245,103 @@ class DeviceRNG:
 
 
 # ----------------------------------------------------------------------------------------------
+# line augmentation of the recogniser pre-training: Tensmeyer brightness + mesh warp on the collated batch (csrc/augment.hip)
+# ----------------------------------------------------------------------------------------------
+AUG_STATS = 258          # per line: Otsu threshold, border level, LUT[256]
+AUG_BRIGHT_SIGMA = 30.0  # utils/augmentation.py:24
+
+
+def warp_lattice(h, w, interval=12):
+    """control lattice of grid_distortion.warp_image (:25-41) -> (src_y [gy], src_x [gx]) fp64: intervals fitted to the image, np.mgrid
+    with a float step (the same numpy expression as the reference, so the end points come out the same)"""
+    import numpy as np
+    w_ratio = max(1, round(w / float(interval)))
+    h_ratio = max(1, round(h / float(interval)))
+    wi, hi = w / w_ratio, h / h_ratio
+    src = np.mgrid[0:h + hi:hi, 0:w + wi:wi]
+    return src[0][:, 0].copy(), src[1][0, :].copy()
+
+
+class LineMesh:
+    """the control lattices of one batch of lines of height H: widths [B] valid columns per line, x_off [B] first valid column (0 unless
+    the batch is centre padded), sigma (scalar or [B]) of the displacements, warp / bright [B] flags (the "low" variant skips either per
+    line); lines of H <= 5 or w <= 5 are not warped (grid_distortion.py:12). disp: None = unit draws from the device generator, or per
+    line (disp_y [gy, gx], disp_x [gy, gx]) explicit displacements (None for an unwarped line) - the teacher-forced path of the tests."""
+
+    def __init__(self, H, widths, sigma=1.5, x_off=None, warp=None, bright=None, disp=None):
+        import numpy as np
+        self.H, self.widths = int(H), [int(w) for w in widths]
+        B = len(self.widths)
+        self.x_off = [0] * B if x_off is None else [int(v) for v in x_off]
+        self.sigma = [float(s) for s in (np.broadcast_to(np.asarray(sigma, dtype=np.float64), (B,)))]
+        self.bright = [True] * B if bright is None else [bool(v) for v in bright]
+        warp = [True] * B if warp is None else [bool(v) for v in warp]
+        self.src = [warp_lattice(self.H, w) if (warp[b] and self.H > 5 and w > 5) else None for b, w in enumerate(self.widths)]
+        self.GY = max([len(s[0]) for s in self.src if s is not None] or [0])
+        self.GX = max([len(s[1]) for s in self.src if s is not None] or [0])
+        self.disp = disp
+        if disp is not None:
+            for s, d in zip(self.src, disp):
+                assert (s is None) or (d is not None and tuple(d[0].shape) == tuple(d[1].shape) == (len(s[0]), len(s[1]))), "displacements do not fit the lattice"
+
+    def tables(self, explicit_fg_bg=None):
+        """-> (lines_i int32 [B,4], lines_f float32 [B, 4+GY+GX], draws float32 [B, 2+2*GY*GX] or None when the draws are made on the device)"""
+        import numpy as np
+        B, GY, GX = len(self.widths), self.GY, self.GX
+        explicit = explicit_fg_bg is not None
+        assert explicit == (self.disp is not None), "explicit brightness draws and explicit displacements go together"
+        li = np.zeros((B, 4), dtype=np.int32)
+        lf = np.zeros((B, 4 + GY + GX), dtype=np.float32)
+        dr = np.zeros((B, 2 + 2 * GY * GX), dtype=np.float32) if explicit else None
+        for b in range(B):
+            s = self.src[b]
+            li[b] = (self.widths[b], 0 if s is None else len(s[0]), 0 if s is None else len(s[1]), self.x_off[b])
+            if explicit:
+                lf[b, :4] = 1.0
+                if self.bright[b]:
+                    dr[b, :2] = explicit_fg_bg[b]
+            else:
+                lf[b, :2] = AUG_BRIGHT_SIGMA if self.bright[b] else 0.0
+                lf[b, 2:4] = self.sigma[b]
+            if s is not None:
+                gy, gx = len(s[0]), len(s[1])
+                lf[b, 4:4 + gy] = s[0]
+                lf[b, 4 + GY:4 + GY + gx] = s[1]
+                if explicit:
+                    dr[b, 2:2 + gy * gx] = np.asarray(self.disp[b][0]).reshape(-1)
+                    dr[b, 2 + gy * gx:2 + 2 * gy * gx] = np.asarray(self.disp[b][1]).reshape(-1)
+        return li, lf, dr
+
+
+def augment_lines(image, mesh, fg_bg=None, want_map=False, rng=None):
+    """Brightness + mesh warp of every line of the collated batch `image` [B,1,H,W] (device, fp32: 1 - level/128, padding -1) in two launches
+    (hwg_augment_stats, hwg_augment_warp) -> a new tensor of the same shape. fg_bg None: the brightness shifts N(0, 30) and the
+    displacements N(0, sigma) are unit draws of `rng` (a DeviceRNG; one hwg_randn launch, the stream offset advances); fg_bg [B,2]
+    (host): explicit shifts, with the explicit displacements of `mesh.disp`. want_map: -> (y, map [B,2,H,W] = (map_y, map_x) in line
+    coordinates, NaN outside the mesh, stats int32 [B,258] = (threshold, border level, LUT))."""
+    B, C, H, W = image.shape
+    assert C == 1 and H == mesh.H and B == len(mesh.widths) and image.is_cuda and image.dtype == torch.float32
+    assert all(0 <= o and w >= 0 and o + w <= W for o, w in zip(mesh.x_off, mesh.widths)), "line extents outside the batch"
+    image = image.contiguous()
+    dev = image.device
+    li, lf, dr = mesh.tables(fg_bg)
+    if dr is None:
+        if rng is None:
+            raise L.HwgError("augment_lines: no explicit draws and no device generator")
+        draws = rng.randn((B, 2 + 2 * mesh.GY * mesh.GX), dev)
+    else:
+        draws = h2d(dr, dev)
+    li_d, lf_d = h2d(li, dev), h2d(lf, dev)
+    stats = torch.empty((B, AUG_STATS), dtype=torch.int32, device=dev)
+    y = torch.empty_like(image)
+    map_out = torch.empty((B, 2, H, W), dtype=torch.float32, device=dev) if want_map else None
+    st = _stream()
+    L.call("hwg_augment_stats", image, li_d, lf_d, lf.shape[1], draws, draws.shape[1], B, H, W, stats, st)
+    L.call("hwg_augment_warp", image, li_d, lf_d, lf.shape[1], draws, draws.shape[1], stats, B, H, W, mesh.GY, mesh.GX, y, map_out, st)
+    return (y, map_out, stats) if want_map else y
+
+
+# ----------------------------------------------------------------------------------------------
 # frozen BatchNorm (eval) and the FusedUpsample weight transform
 # ----------------------------------------------------------------------------------------------
 def norm_apply_frozen(x, running_mean, running_var, eps, gamma, beta, act=ACT_NONE, slope=0.0):

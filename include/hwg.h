@@ -487,6 +487,29 @@ int hwg_insert_spaces_plan(const float* counts, const int* label_lengths, int L,
 int hwg_insert_spaces_fill(const int* label, const int* label_lengths, const int* reps, const int* starts, int L, int B, int T, int* idx,
                            void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Line augmentation of the recogniser pre-training on the collated batch: Tensmeyer brightness + mesh warp
+ * (utils/augmentation.py:5-31 tensmeyer_brightness / apply_tensmeyer_brightness, utils/grid_distortion.py:11-66 warp_image; called per
+ * line from datasets/hw_dataset.py:143-152, datasets/author_hw_dataset.py:429-432, datasets/author_rimeslines_dataset.py:428-434).
+ * x / y: [B][H][W] fp32 images holding 1 - level/128 (levels 0..255), padding columns -1. Per-line tables on the device:
+ *   lines_i [B][4] int32 = {valid width w, lattice rows gy (0: no warp), lattice columns gx, first valid column x_off};
+ *   lines_f [B][lf_stride] = {foreground scale, background scale, row sigma, column sigma, src_y[GY], src_x[GX]}: the control lattice of
+ *     grid_distortion.py:25-41 (src_y[i], src_x[j] = the np.mgrid coordinates), GY / GX = the batch's largest gy / gx;
+ *   draws [B][draw_stride] = {fg, bg, row displacement [gy][gx], column displacement [gy][gx]}: unit draws (hwg_randn) that the kernels
+ *     multiply by the scales / sigmas of lines_f, or explicit values with scales of 1.
+ * hwg_augment_stats: stats [B][258] int32 = {Otsu threshold t (lowest level maximising the between-class variance, fp64), border level m =
+ *   round-half-even(mean of the re-lit line), LUT q(p) = trunc(clamp(p + (p > t ? bg : fg), 0, 255)) in fp32}; one workgroup per line.
+ * hwg_augment_warp: y = bilinear resample (taps outside the line = m, result rounded half to even to a level) of the LUT-mapped line at the
+ *   inverse map = piecewise-linear interpolation of lattice -> lattice + displacement over the lattice cells, each split along the diagonal
+ *   that is locally Delaunay (what scipy.interpolate.griddata(destination, source, pixels, "linear") computes wherever every lattice
+ *   triangle is a Delaunay triangle); pixels outside the mesh take m; lines with gy = 0, H <= 5 or w <= 5 get the LUT only
+ *   (grid_distortion.py:12). map_out (optional, tests): [B][2][H][W] = (map_y, map_x) in line coordinates, NaN outside the mesh / the line.
+ * ------------------------------------------------------------------------------------------ */
+int hwg_augment_stats(const float* x, const int* lines_i, const float* lines_f, int lf_stride, const float* draws, int draw_stride,
+                      int B, int H, int W, int* stats, void* stream);
+int hwg_augment_warp(const float* x, const int* lines_i, const float* lines_f, int lf_stride, const float* draws, int draw_stride,
+                     const int* stats, int B, int H, int W, int GY, int GX, float* y, float* map_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,8 +2,9 @@
 """python train.py -c configs/<cfg>.json [-r checkpoint] [-s soft_checkpoint] [-g gpu]
 Drop-in for the reference's train.py: classes are resolved by the names in the config (arch / loss / trainer.class), the
 config's `name` must match its file name, SIGINT saves a checkpoint. Under torchrun (WORLD_SIZE>1) every rank trains on its
-own author shard and gradients are all-reduced over RCCL. Real datasets (IAM/RIMES images) are outside the accelerated path;
-`--synthetic` drives the trainer with synthetic author batches of the configured shape."""
+own author shard and gradients are all-reduced over RCCL. A dataset directory in the reference's layout (IAM / RIMES) is read through
+data.getDataLoader - the recogniser pre-training configs' brightness + mesh-warp augmentation runs on the GPU -; `--synthetic` drives the
+trainer with synthetic author batches of the configured shape instead."""
 import argparse
 import json
 import logging

@@ -19,7 +19,9 @@ __device__ __forceinline__ void hwg_philox4(uint64_t seed, uint64_t ctr, uint32_
   for (int r = 0; r < 10; ++r) hwg_philox_round(c, k);
   out[0] = c[0]; out[1] = c[1]; out[2] = c[2]; out[3] = c[3];
 }
-__device__ __forceinline__ float hwg_u01(uint32_t x) { return ((float)(x >> 8) + 0.5f) * (1.f / 16777216.f); }  // (0,1)
+// (0,1]: from x >> 8 = 2^23 on the sum with 0.5 is a tie and rounds to the even neighbour, so x >> 8 = 2^24 - 1 gives 2^24 and the result
+// is exactly 1 (2^-25 at x >> 8 = 0). Both users are safe with it: logf(1) = 0, and a keep test u >= p holds.
+__device__ __forceinline__ float hwg_u01(uint32_t x) { return ((float)(x >> 8) + 0.5f) * (1.f / 16777216.f); }
 // the four standard normals of counter `ctr` (elements 4*ctr .. 4*ctr+3 of the stream)
 __device__ __forceinline__ float4 hwg_randn4(uint64_t seed, uint64_t ctr) {
   uint32_t r[4];

@@ -123,6 +123,19 @@ def test_call_thunks_refuse_values_that_do_not_fit_the_c_types():
         L.call("hwg_conv_pack_weight", None, None, 1 << 33, *([1] * 9), None)   # int A (13 arguments: checked before the call is made)
 
 
+def test_call_thunks_pass_the_whole_unsigned_64_bit_range():
+    """`unsigned long long` parameters (the Philox seed and stream offset) take every value below 2^64 - a seed with its top bit set used to
+    be refused by the thunk though the C-ABI and the ctypes path take it - and nothing outside it. The calls below fail the library's own
+    argument check (no output buffer) before anything is launched: what is under test is that the integers get that far."""
+    from handwriting_line_generation_amd import _lib as L
+    for seed, offset in (((1 << 64) - 1, (1 << 64) - 1), (1 << 63, 0), (0x9E3779B97F4A7C15, 12345)):
+        with pytest.raises(L.HwgError):
+            L.call("hwg_randn", None, 4, seed, offset, None)
+    for seed, offset in ((1 << 64, 0), (0, 1 << 64), (-1, 0), (0, -1)):
+        with pytest.raises(OverflowError):
+            L.call("hwg_randn", None, 4, seed, offset, None)
+
+
 def test_replay_executor_runs_a_call_list_and_classifies_stream_parameters():
     """the C launch-list executor behind replay.py (csrc/hwg_pycall.c, generated): a list of status-returning entry points runs in one call, stops at
     the first non-zero status and reports its index; malformed lists are refused before anything is called; the table it is driven by marks every

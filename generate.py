@@ -1,0 +1,248 @@
+#!/usr/bin/env python
+"""python generate.py -c checkpoint.pth -d out_dir [-g gpu] [-f config.json] [-a k=v,...] -s styles.pkl -r choice=R,num=N,text=...
+python generate.py -c checkpoint.pth -d out_dir -r choice=f,path1=a.png,path2=b.png,text=...
+Non-interactive drop-in for the reference's generate.py flags: `R` writes N lines in styles sampled (and interpolated) from a style file,
+`f` interpolates between the styles of two line images in 20 steps. Lines are rendered in batches of equal label length, converted to
+8-bit grey and cut to their own width on the GPU, and written as PNGs by a thread pool - or, with --shard N, as lines_%05d.npz arrays of N
+lines each (pixels uint8 1-D, offsets int64 [n+1], widths int32 [n], index int64 [n]). The texts go to <savedir>/OUT.txt as `i:text`."""
+import argparse
+import collections
+import os
+import random
+import sys
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, ROOT)
+
+PANGRAM = "The quick brown fox jumps over the lazy dog."
+CHOICES = ("R", "f")
+MAX_WRITERS = 16
+
+
+def parse_addtoconfig(arg):
+    """'-a k1=v1,k2=k3=v2' -> [[k1, v1], [k2, k3, v2]] (reference generate.py:941-946: items split at ',', keys and value at '='). An item
+    without '=' (where the reference fails with an IndexError) is read as a key in front of the next item: 'k2,k3=v2' is 'k2=k3=v2'."""
+    out, prefix = [], []
+    for kv in (arg.split(",") if arg else []):
+        parts = kv.split("=")
+        if len(parts) == 1:
+            prefix.append(parts[0])
+        else:
+            out.append(prefix + parts)
+            prefix = []
+    if prefix:
+        raise SystemExit("generate.py: -a %r ends in keys without a value" % arg)
+    return out
+
+
+def parse_run(arg):
+    """'-r key=value,...' -> dict (reference generate.py:953-958)"""
+    out = {}
+    for pair in arg.split(","):
+        ss = pair.split("=")
+        if len(ss) < 2:
+            raise SystemExit("generate.py: -r takes key=value pairs, got %r" % pair)
+        out[ss[0]] = ss[1]
+    return out
+
+
+def seed_everything(seed):
+    """numpy, torch, Python's random, the device Philox stream -> the random.Random that samples the styles"""
+    import torch
+    from handwriting_line_generation_amd import rng
+    rng.seed_process(seed)
+    np.random.seed(seed)
+    torch.manual_seed(seed)
+    return random.Random(seed)
+
+
+def write_png(path, line):
+    """one uint8 [H, w] line as an 8-bit grey PNG"""
+    from PIL import Image
+    line = np.ascontiguousarray(line, dtype=np.uint8)
+    Image.frombuffer("L", (line.shape[1], line.shape[0]), line, "raw", "L", 0, 1).save(path, format="PNG")
+
+
+def write_shard(path, lines, index):
+    """ragged uint8 lines [H, w_k] -> one .npz: pixels uint8 1-D (the lines back to back, row-major), offsets int64 [n+1], widths int32 [n],
+    index int64 [n] (which text each line renders)"""
+    sizes = np.asarray([l.size for l in lines], dtype=np.int64)
+    offsets = np.zeros(len(lines) + 1, dtype=np.int64)
+    np.cumsum(sizes, out=offsets[1:])
+    pixels = np.concatenate([np.ascontiguousarray(l, dtype=np.uint8).reshape(-1) for l in lines]) if lines else np.zeros(0, np.uint8)
+    np.savez(path, pixels=pixels, offsets=offsets, widths=np.asarray([l.shape[1] for l in lines], dtype=np.int32),
+             index=np.asarray(index, dtype=np.int64))
+
+
+def read_shard(path, height=64):
+    """-> [(index, uint8 [height, w])] of a file written by write_shard"""
+    with np.load(path) as z:
+        pixels, offsets, widths, index = z["pixels"], z["offsets"], z["widths"], z["index"]
+    return [(int(index[k]), pixels[offsets[k]:offsets[k + 1]].reshape(height, int(widths[k]))) for k in range(len(widths))]
+
+
+class LineSink:
+    """takes (index, line) pairs and leaves files in `savedir`: `pattern % index` PNGs, or lines_%05d.npz per `shard` lines; the encoding
+    runs on `writers` threads (zlib releases the GIL), with a bounded backlog so that the renderer cannot run away from the encoders"""
+
+    def __init__(self, savedir, pattern, shard=0, writers=8):
+        self.savedir, self.pattern, self.shard = savedir, pattern, int(shard)
+        workers = min(max(int(writers), 1), MAX_WRITERS)
+        self.pool = ThreadPoolExecutor(max_workers=workers)
+        self.backlog = collections.deque()
+        self.limit = 2 if self.shard else 64 * workers
+        self.lines, self.index, self.n_shards, self.count = [], [], 0, 0
+
+    def _submit(self, fn, *args):
+        while len(self.backlog) >= self.limit:
+            self.backlog.popleft().result()
+        self.backlog.append(self.pool.submit(fn, *args))
+
+    def _flush(self):
+        if self.lines:
+            self._submit(write_shard, os.path.join(self.savedir, "lines_%05d.npz" % self.n_shards), self.lines, self.index)
+            self.lines, self.index, self.n_shards = [], [], self.n_shards + 1
+
+    def add(self, index, line):
+        self.count += 1
+        if not self.shard:
+            self._submit(write_png, os.path.join(self.savedir, self.pattern % index), line)
+            return
+        self.lines.append(line)
+        self.index.append(index)
+        if len(self.lines) == self.shard:
+            self._flush()
+
+    def close(self):
+        self._flush()
+        try:
+            for f in self.backlog:
+                f.result()
+        finally:
+            self.pool.shutdown(wait=True)
+
+
+def pick_texts(text, num, config):
+    """the `text` argument of the R action (reference generate.py:358-378) -> num texts"""
+    from handwriting_line_generation_amd.data.text_data import TextData
+    if len(text) == 0:
+        return [PANGRAM] * num
+    if text == "RANDOM":
+        corpus = config.get("trainer", {}).get("text_data")
+        if not corpus or not os.path.exists(corpus):
+            raise SystemExit("generate.py: text=RANDOM samples the training corpus, but trainer.text_data %r does not exist; "
+                             "pass text=<file>.txt" % corpus)
+        return TextData(batch_size=num, max_len=55, textfile=corpus).getInstance()["gt"]
+    if text.endswith(".txt"):
+        return TextData(batch_size=num, max_len=55, textfile=text).getInstance()["gt"]
+    return [text] * num
+
+
+def run_R(model, config, char_to_idx, run, args, rand, gpu):
+    from handwriting_line_generation_amd.generate import load_style_file, render_lines, sample_styles
+    if args.style_loc is None:
+        raise SystemExit("generate.py: choice=R samples its styles from a style file: pass -s path/to/styles.pkl")
+    num = int(run.get("num", run.get("num_inst", 0)))
+    if num < 1:
+        raise SystemExit("generate.py: choice=R needs num=<lines to generate>")
+    texts = pick_texts(run.get("text", ""), num, config)
+    styles = sample_styles(load_style_file(args.style_loc), num, rand)
+    sink = LineSink(args.savedir, "sample_%d.png", args.shard, args.writers)
+    skipped = []
+    try:
+        for i, line in render_lines(model, texts, styles, char_to_idx, gpu, batch_lines=args.batch, skipped=skipped):
+            sink.add(i, line)
+    finally:
+        sink.close()
+    with open(os.path.join(args.savedir, "OUT.txt"), "w") as out:
+        for i, text in enumerate(texts):
+            if i not in skipped:
+                out.write("%d:%s\n" % (i, text))
+    return sink.count
+
+
+def run_f(model, config, char_to_idx, run, args, gpu):
+    import torch
+    from handwriting_line_generation_amd import ops
+    from handwriting_line_generation_amd.generate import interpolate, style_from_images
+    if "path1" not in run or "path2" not in run:
+        raise SystemExit("generate.py: choice=f needs path1=<image>,path2=<image>")
+    text = run["text_gen"] if "text_gen" in run else run.get("text", "")
+    if len(text) == 0:
+        raise SystemExit("generate.py: choice=f needs text=<text to write>")
+    style = style_from_images(model, [run["path1"], run["path2"]], gpu)
+    model.count_std = model.dup_std = 0          # reference generate.py:199-200
+    sink = LineSink(args.savedir, "%s.png", args.shard, args.writers)
+    try:
+        with torch.no_grad():
+            images, _ = interpolate(model, style[0:1].contiguous(), style[1:2].contiguous(), text, char_to_idx, gpu, step=0.05)
+            for i, image in enumerate(images):
+                B, _, H, W = image.shape
+                pixels, offsets = ops.lines_to_u8(image, [W] * B)
+                host = pixels.cpu().numpy()
+                for b in range(B):
+                    line = host[offsets[b]:offsets[b + 1]].reshape(H, W)
+                    if args.shard:
+                        sink.add(b * len(images) + i, line)
+                    else:
+                        sink.add("gen%d_%d" % (b, i), line)
+    finally:
+        sink.close()
+    return sink.count
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description="MI355X-native handwriting line generation from a checkpoint")
+    ap.add_argument("-c", "--checkpoint", type=str, default=None, help="checkpoint of this package or of the reference")
+    ap.add_argument("-d", "--savedir", type=str, default=None, help="directory the images are written to")
+    ap.add_argument("-g", "--gpu", type=int, default=0)
+    ap.add_argument("-f", "--config", type=str, default=None, help="config file to use instead of the checkpoint's")
+    ap.add_argument("-a", "--addtoconfig", type=str, default=None, help="k1=v1,k2=k3=v2: config[k1]=v1, config[k2][k3]=v2 (int / float coerced, empty = null)")
+    ap.add_argument("-r", "--run", type=str, default=None, help="choice=R,num=N,text=... | choice=f,path1=..,path2=..,text=..")
+    ap.add_argument("-s", "--style_loc", type=str, default=None, help="style pickle (prefix) written by evaluate.dump_styles")
+    ap.add_argument("--seed", type=int, default=1234)
+    ap.add_argument("--batch", type=int, default=64, help="lines rendered per batch")
+    ap.add_argument("--shard", type=int, default=0, help="write lines_%%05d.npz arrays of this many lines instead of PNGs")
+    ap.add_argument("--writers", type=int, default=8, help="encoder threads (at most %d)" % MAX_WRITERS)
+    args = ap.parse_args(argv)
+
+    if args.run is None:
+        raise SystemExit("generate.py: the interactive prompt is not built; pass -r choice=R,num=N,text=... (with -s styles) or "
+                         "-r choice=f,path1=..,path2=..,text=..")
+    run = parse_run(args.run)
+    choice = run.get("choice", "")
+    if choice not in CHOICES:
+        raise NotImplementedError("generate.py: action %r is not built; the two that exist are 'R' (random interpolated styles from a style "
+                                  "file) and 'f' (interpolation between the styles of two line images)" % choice)
+    if args.checkpoint is None:
+        raise SystemExit("generate.py: must provide a checkpoint (with -c)")
+    if args.savedir is None:
+        raise SystemExit("generate.py: must provide a directory to write to (with -d)")
+    if args.batch < 1 or args.shard < 0:
+        raise SystemExit("generate.py: --batch must be at least 1 and --shard non-negative")
+
+    import torch
+    torch.set_num_threads(1)       # host side = many tiny CPU ops; the intra-op pool only adds latency (see bench.py)
+    from handwriting_line_generation_amd.generate import load_for_generation
+    rand = seed_everything(args.seed)
+    torch.cuda.set_device(args.gpu)
+    gpu = torch.device("cuda", args.gpu)
+    model, config, char_to_idx = load_for_generation(args.checkpoint, args.config, args.gpu, add_to_config=parse_addtoconfig(args.addtoconfig))
+    os.makedirs(args.savedir, exist_ok=True)
+
+    t0 = time.time()
+    if choice == "R":
+        n = run_R(model, config, char_to_idx, run, args, rand, gpu)
+    else:
+        n = run_f(model, config, char_to_idx, run, args, gpu)
+    torch.cuda.synchronize()
+    dt = time.time() - t0
+    print("lines %d  seconds %.3f  lines/s %.1f" % (n, dt, n / dt if dt > 0 else 0.0), flush=True)
+
+
+if __name__ == "__main__":
+    main()

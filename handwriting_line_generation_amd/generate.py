@@ -102,3 +102,206 @@ def interpolate(model, style1, style2, text, char_to_idx, gpu, step=0.05):
         results.append(model(label, label_len, style))
         styles.append(style.cpu().detach())
     return results, styles
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# from a checkpoint to pictures: what the reference's `generate.py -c ... -d ... -s ...` program does around the calls above
+def apply_add_to_config(config, adds):
+    """the reference's `-a` rule (generate.py:116-136): every entry [k1, ..., kn, value] sets config[k1]...[kn] = value, the value coerced
+    to int, else float, else kept as text; an empty value is None"""
+    for add in adds or []:
+        if len(add) < 2:
+            raise ValueError("config addition %r: expected key=value (nested: key=key=value)" % "=".join(add))
+        target = config
+        for key in add[:-2]:
+            target = target[key]
+        value = add[-1]
+        if value == "":
+            value = None
+        else:
+            try:
+                value = int(value)
+            except ValueError:
+                try:
+                    value = float(value)
+                except ValueError:
+                    pass
+        target[add[-2]] = value
+    return config
+
+
+def load_for_generation(checkpoint_path, config_path=None, gpu=0, add_to_config=None):
+    """-> (model, config, char_to_idx) for a checkpoint of this package or of the reference (generate.py:88-106, 187-209): the model alone, in
+    eval mode on `gpu` - no trainer, no optimizer, no data loader. `style_from_normal*` weights are dropped and `pretrained*` entries of the
+    config cleared as the reference does; `add_to_config` entries (apply_add_to_config) are applied before the model is built; a `data_loader.char_file` that does not exist falls back to the packaged file of that name."""
+    import json
+    import os
+    from . import model as models
+    from .logger import load_checkpoint
+    checkpoint = load_checkpoint(checkpoint_path)
+    state = {k: v for k, v in checkpoint["state_dict"].items() if "style_from_normal" not in k}
+    if config_path is None:
+        config = checkpoint["config"]
+    else:
+        with open(config_path) as f:
+            config = json.load(f)
+    for key in config:
+        if "pretrained" in key:
+            config[key] = None
+    config["model"]["RUN"] = True        # (a missing model.pretrained_hwr file is not an error: the state dict carries the recogniser)
+    config["cuda"], config["gpu"] = True, gpu
+    apply_add_to_config(config, add_to_config)
+    arch = config.get("arch", "HWWithStyle")
+    if arch != "HWWithStyle":
+        raise NotImplementedError("generation needs an HWWithStyle checkpoint, this one holds %r" % arch)
+    model = getattr(models, arch)(config["model"])
+    model.load_state_dict(state)
+    model = model.to(torch.device("cuda", gpu) if isinstance(gpu, int) else gpu)
+    model.eval()
+    char_file = config["data_loader"]["char_file"]
+    if not os.path.exists(char_file):
+        char_file = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data", os.path.basename(char_file))
+    with open(char_file) as f:
+        char_to_idx = json.load(f)["char_to_idx"]
+    return model, config, char_to_idx
+
+
+def read_style_image(path, img_height=64):
+    """one line image as the reference's `f` action reads it (generate.py:655-663): grey, resized bicubic to `img_height` rows when it has
+    another height (PIL here, OpenCV there), 1 - x / 128 -> float32 [1, H, W] on the host"""
+    from PIL import Image
+    im = Image.open(path).convert("L")
+    if im.size[1] != img_height:
+        percent = float(img_height) / im.size[1]
+        im = im.resize((max(int(round(im.size[0] * percent)), 1), img_height), Image.BICUBIC)
+    return torch.from_numpy(1.0 - np.asarray(im, dtype=np.float32)[None] / 128.0)
+
+
+def style_from_images(model, paths, gpu):
+    """style vectors [n, style_dim] of the line images at `paths` (the reference's `f` action, generate.py:653-686): all cropped to the
+    narrowest one, stacked, one extract_style(stack, None, 1) call. Without a label there is nothing to align, so the extractor reads the
+    recogniser's own prediction for the call."""
+    images = [read_style_image(p, model.image_height) for p in paths]
+    min_width = min(im.shape[2] for im in images)
+    stack = ops.h2d(torch.stack([im[:, :, :min_width] for im in images], dim=0).contiguous(), gpu)
+    old = model.use_hwr_pred_for_style
+    model.use_hwr_pred_for_style = True
+    try:
+        model.pred = model.spaced_label = model.spaced_label_index = None
+        with torch.no_grad():
+            return model.extract_style(stack, None, 1)
+    finally:
+        model.use_hwr_pred_for_style = old
+        model.pred = model.spaced_label = model.spaced_label_index = None
+
+
+def load_style_file(style_loc):
+    """the style pickle(s) evaluate.dump_styles / the reference's get_styles.py write -> {author: [style, ...]} (generate.py:215-239:
+    `style_loc` is a prefix, every file matching style_loc + '*' is read, with or without the `ids` entry). Authors keep the order in which
+    the (sorted) files name them, so that a seed reproduces."""
+    import pickle
+    from glob import glob
+    if not style_loc.endswith("*"):
+        style_loc += "*"
+    files = sorted(glob(style_loc))
+    if not files:
+        raise FileNotFoundError("no style file matches %r" % style_loc)
+    styles = {}
+    for loc in files:
+        with open(loc, "rb") as f:
+            data = pickle.load(f)
+        for i, author in enumerate(data["authors"]):
+            styles.setdefault(author, []).append(np.asarray(data["styles"][i]))
+    return styles
+
+
+def sample_styles(styles_by_author, n, rand):
+    """n styles drawn as the reference's `R` action draws them (generate.py:385-405): per instance choice(authors), randint(0, len - 1),
+    choice(authors), randint(0, len - 1), random() from `rand` (a random.Random), inter = 2 r - 0.5 (extrapolates a quarter beyond either end),
+    style = s1 * inter + s2 * (1 - inter) -> float32 [n, style_dim] on the host"""
+    authors = list(styles_by_author.keys())
+    out = []
+    for _ in range(n):
+        a = rand.choice(authors)
+        s1 = styles_by_author[a][rand.randint(0, len(styles_by_author[a]) - 1)]
+        b = rand.choice(authors)
+        s2 = styles_by_author[b][rand.randint(0, len(styles_by_author[b]) - 1)]
+        inter = 2 * rand.random() - 0.5
+        out.append(np.asarray(s1 * inter + s2 * (1 - inter), dtype=np.float32).reshape(-1))
+    return np.stack(out) if out else np.zeros((0, 0), dtype=np.float32)
+
+
+def bucket_by_length(texts, char_to_idx, batch_lines=64):
+    """-> (batches, skipped): `batches` a list of (label length, [text indices]) in which every batch holds only texts that encode to the
+    same number of labels (characters missing from `char_to_idx` are dropped first, as str2label_single drops them), at most `batch_lines`
+    of them, lengths in order of first appearance; `skipped` the indices of texts that encode to no label at all."""
+    if batch_lines < 1:
+        raise ValueError("batch_lines must be at least 1")
+    by_len, skipped = {}, []
+    for i, text in enumerate(texts):
+        n = len(string_utils.str2label_single(text, char_to_idx))
+        if n == 0:
+            skipped.append(i)
+        else:
+            by_len.setdefault(n, []).append(i)
+    batches = []
+    for n, idx in by_len.items():
+        batches.extend((n, idx[k:k + batch_lines]) for k in range(0, len(idx), batch_lines))
+    return batches, skipped
+
+
+def line_widths(padded, image_width):
+    """columns of each line of a batch that are its own: 4 * (T - round(padded[b] * T)) with T = image_width / 4 content steps, clamped to
+    [4, image_width] (`padded`: the blank-tail fractions generate_stream yields)"""
+    T = image_width // 4
+    return [min(max(4 * (T - int(round(p * T))), 4), image_width) for p in padded]
+
+
+def _bucket_requests(texts, styles, char_to_idx, batches, gpu):
+    for n, idx in batches:
+        label = np.stack([string_utils.str2label_single(texts[i], char_to_idx).astype(np.int32) for i in idx], axis=1)
+        style = styles[torch.as_tensor(idx, dtype=torch.long, device=styles.device)]
+        yield torch.from_numpy(label), torch.IntTensor(len(idx)).fill_(n), ops.h2d(style.contiguous(), gpu)
+
+
+def render_lines(model, texts, styles, char_to_idx, gpu, batch_lines=64, skipped=None):
+    """Generator over (index, uint8 numpy [64, w]) for every text, text i in style styles[i] ([n, style_dim], host or device), in any order:
+    the picture the reference writes (generate.py:426), cut to the line's own width.
+
+    Lines are batched BY LABEL LENGTH (bucket_by_length): the spacer convolves over the label axis, and a shorter line's padding labels
+    (class 0 one-hot, not zeros) would reach into its last characters; with equal lengths no line sees another's padding, so a line's
+    spacing depends on its own text and style only. The batches go through generate_stream; each image is converted and packed ragged on
+    the GPU (ops.lines_to_u8) and fetched on the copy stream while the next batch renders - one fetch in flight. count_std / dup_std are 0
+    for the duration (generate.py:199-200) and restored when the generator ends or is closed. Texts that encode to no label are skipped
+    with a warning (their indices are appended to `skipped` when a list is given)."""
+    import logging
+    styles = torch.as_tensor(styles)
+    batches, skip = bucket_by_length(texts, char_to_idx, batch_lines)
+    if skip:
+        logging.getLogger("generate").warning("render_lines: %d text(s) hold no character of the character set, skipped: %s", len(skip), skip)
+        if skipped is not None:
+            skipped.extend(skip)
+    std = (model.count_std, model.dup_std)
+    model.count_std = model.dup_std = 0
+    try:
+        stream = generate_stream(model, _bucket_requests(texts, styles, char_to_idx, batches, gpu), gpu)
+        pending = None
+        for _, idx in batches:
+            with torch.no_grad():           # (not around the yields: a suspended generator would leave the caller's gradients off)
+                image, padded = next(stream)
+            if pending is not None:
+                yield from _cut_lines(*pending)
+            with torch.no_grad():
+                widths = line_widths(padded, image.shape[3])
+                pixels, offsets = ops.lines_to_u8(image, widths)
+                pending = (idx, ops.AsyncFetch(pixels), offsets, widths, image.shape[2])
+        if pending is not None:
+            yield from _cut_lines(*pending)
+    finally:
+        model.count_std, model.dup_std = std
+
+
+def _cut_lines(idx, fetch, offsets, widths, height):
+    host = fetch.get().numpy()
+    for b, i in enumerate(idx):
+        yield i, host[offsets[b]:offsets[b + 1]].reshape(height, widths[b]).copy()      # (a copy: the pinned staging buffer is reused)

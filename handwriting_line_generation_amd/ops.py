@@ -2342,6 +2342,46 @@ def augment_lines(image, mesh, fg_bg=None, want_map=False, rng=None):
 
 
 # ----------------------------------------------------------------------------------------------
+# generated lines as 8-bit grey pictures, ragged (csrc/lines_out.hip)
+# ----------------------------------------------------------------------------------------------
+def lines_to_u8(img, widths, out=None, offsets=None):
+    """The generator's image `img` [B,1,H,W] (device, fp32 in [-1, 1]) -> (pixels, offsets): `pixels` a uint8 1-D device tensor in which
+    line b is the finished H x widths[b] grey picture pixels[offsets[b]:offsets[b + 1]] (the reference's ((1 - im) * 127.5).astype(uint8),
+    cut to the line's own width), `offsets` a host int64 [B+1] array. `widths` is a host list / array: multiples of 4 in [4, W], validated
+    here, before anything is uploaded or launched. `out`: a uint8 device buffer of at least offsets[B] bytes to write into; `offsets`
+    [B+1] places the lines explicitly (multiples of 4; offsets[B] = the bytes in use) instead of back to back."""
+    import numpy as np
+    if img.dim() != 4 or img.shape[1] != 1 or not img.is_cuda or img.dtype != torch.float32:
+        raise L.HwgError("lines_to_u8: img must be a [B,1,H,W] fp32 device tensor, got %s %s" % (tuple(img.shape), img.dtype))
+    B, _, H, W = img.shape
+    w = np.asarray(widths, dtype=np.int64).reshape(-1)
+    if B < 1 or w.shape[0] != B:
+        raise L.HwgError("lines_to_u8: %d widths for a batch of %d lines" % (w.shape[0], B))
+    if W % 4:
+        raise L.HwgError("lines_to_u8: image width %d is not a multiple of 4" % W)
+    if ((w < 4) | (w > W) | (w % 4 != 0)).any():
+        raise L.HwgError("lines_to_u8: widths must be multiples of 4 in [4, %d], got %s" % (W, w.tolist()))
+    if offsets is None:
+        offsets = np.zeros(B + 1, dtype=np.int64)
+        np.cumsum(H * w, out=offsets[1:])          # multiples of 4, as the kernel's 32-bit stores need
+    else:
+        offsets = np.asarray(offsets, dtype=np.int64).reshape(-1)
+        if offsets.shape[0] != B + 1 or (offsets % 4 != 0).any() or (offsets[:B] < 0).any() or (offsets[:B] + H * w > offsets[B]).any():
+            raise L.HwgError("lines_to_u8: offsets must be %d multiples of 4 with every line inside [0, offsets[B]), got %s" % (B + 1, offsets.tolist()))
+    total = int(offsets[B])
+    if out is None:
+        out = torch.empty((total,), dtype=torch.uint8, device=img.device)
+    elif not out.is_cuda or out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() < total:
+        raise L.HwgError("lines_to_u8: out must be a contiguous uint8 device buffer of at least %d bytes" % total)
+    table = np.empty(3 * B, dtype=np.int32)      # offsets [B] int64 first (8-byte aligned), then widths [B] int32: one upload
+    table[:2 * B].view(np.int64)[:] = offsets[:B]
+    table[2 * B:] = w
+    table_d = h2d(table, img.device)
+    L.call("hwg_lines_to_u8", img.contiguous(), B, H, W, table_d[2 * B:], table_d[:2 * B], out, _stream())
+    return out[:total], offsets
+
+
+# ----------------------------------------------------------------------------------------------
 # frozen BatchNorm (eval) and the FusedUpsample weight transform
 # ----------------------------------------------------------------------------------------------
 def norm_apply_frozen(x, running_mean, running_var, eps, gamma, beta, act=ACT_NONE, slope=0.0):

@@ -510,6 +510,17 @@ int hwg_augment_stats(const float* x, const int* lines_i, const float* lines_f, 
 int hwg_augment_warp(const float* x, const int* lines_i, const float* lines_f, int lf_stride, const float* draws, int draw_stride,
                      const int* stats, int B, int H, int W, int GY, int GX, float* y, float* map_out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Generated lines as 8-bit grey pictures, ragged (generate.py:303, 344, 426, 496, 525, 622, 692, 718, 786:
+ * ((1 - im) * 127.5).astype(np.uint8), there on the host after downloading the padded fp32 batch).
+ * img: the generator's image [B][1][H][W] fp32; widths [B] int32 and offsets [B] int64 on the device: line b becomes the H x widths[b]
+ * picture out[offsets[b] : offsets[b] + H * widths[b]] (row stride widths[b]); columns >= widths[b] are never read.
+ * Pixel: (1 - x) * 127.5 in fp32, clamped to [0, 255] (numpy wraps outside [-1, 1]), NaN -> 0, truncated toward zero.
+ * W % 4 == 0 (checked here); 4 <= widths[b] <= W, widths[b] % 4 == 0 and offsets[b] % 4 == 0 are the caller's to check (device arrays:
+ * ops.lines_to_u8 validates them on the host before the upload). One 16-byte load and one 32-bit store per lane.
+ * ------------------------------------------------------------------------------------------ */
+int hwg_lines_to_u8(const float* img, int B, int H, int W, const int* widths, const long long* offsets, unsigned char* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,7 @@
 
 namespace {
 
-// patches[i][j][c] = x[b_i][pos_i - w + j][c] (zero outside [0,Wx)), j in [0, 2w+1)
+// patches[i][j][c] = x[b_i][pos_i - w + j][c] (zero outside [0,Wx); all zero for a centre (b_i, pos_i) outside the tensor), j in [0, 2w+1)
 __global__ void gather_windows_kernel(const float* x, int B, int Wx, int C, const int* idx_b, const int* idx_pos, int n, int w, float* patches) {
   const int WW = 2 * w + 1;
   const long long total = (long long)n * WW * C;
@@ -13,9 +13,11 @@ __global__ void gather_windows_kernel(const float* x, int B, int Wx, int C, cons
     const long long t = i / C;
     const int j = (int)(t % WW);
     const int k = (int)(t / WW);
-    const int pos = idx_pos[k] - w + j;
+    const int ctr = idx_pos[k];
+    const int pos = ctr - w + j;
     const int b = idx_b[k];
-    patches[i] = (pos >= 0 && pos < Wx && b >= 0 && b < B) ? x[((long long)b * Wx + pos) * C + c] : 0.f;
+    // a window whose centre lies outside the tensor is all zeros, also where it reaches back inside: the backward pass ignores such windows
+    patches[i] = (pos >= 0 && pos < Wx && ctr >= 0 && ctr < Wx && b >= 0 && b < B) ? x[((long long)b * Wx + pos) * C + c] : 0.f;
   }
 }
 // dx[b][pos][c] = sum over the windows that cover (b, pos) of dpatches[k][j][c]. The windows overlap, so a scatter would need floating
@@ -191,7 +193,9 @@ __global__ __launch_bounds__(256) void linear_bank_wgrad_kernel(const float* __r
     d[b] = (b < B) ? dy[(long long)b * C + c] : 0.f;
     bs += d[b];
   }
-  if (!gwptr[l]) return;   // layer frozen
+  // (the bias first: a layer whose weight is frozen may still train its bias)
+  if (lane == 0 && gbptr && gbptr[l]) reinterpret_cast<float*>(gbptr[l])[o] += bs;
+  if (!gwptr[l]) return;   // weight frozen
   float* gW = reinterpret_cast<float*>(gwptr[l]) + (long long)o * I;
   for (int i = lane; i < I; i += 64) {
     float s = 0.f;
@@ -200,7 +204,6 @@ __global__ __launch_bounds__(256) void linear_bank_wgrad_kernel(const float* __r
       if (b < B) s += d[b] * x[(long long)b * I + i];
     gW[i] += s;
   }
-  if (lane == 0 && gbptr && gbptr[l]) reinterpret_cast<float*>(gbptr[l])[o] += bs;
 }
 // input gradient: dx[b][i] = sum_l sum_o dy_l[b][o] W_l[o][i]. Stage 1: workgroup c sums its chunk of LB_OCHUNK neurons for all rows
 // (thread = (b, i), weight rows read coalesced along i and shared by the B rows) into part[c][b][i]; stage 2 adds the chunks in order.

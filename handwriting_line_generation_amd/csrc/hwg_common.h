@@ -78,6 +78,7 @@ struct HwgTune {
   int c1_rows;           // HWG_C1_ROWS: 0 = single-input-channel forward convs on the gather kernels (A/B timing), 1 default = input rows staged in LDS, filter in registers
   int split_inkernel;    // HWG_SPLIT_INKERNEL: 0 default = split-K / channel-split partial images summed by a reduce launch; 1 = by the wavefront / workgroup that delivers a tile's LAST partial (bit-identical; measured SLOWER in the step - what crosses XCDs has to bypass the L2s -, kept for A/B runs: profiles/r06_inkernel_sums.txt)
   int norm_fused;        // HWG_NORM_FUSED: 0 default = moments pass and apply pass of the per-sample normalisations as two launches; 1 = one launch per direction with a barrier over the sample's workgroups (bit-identical; measured SLOWER in the step, kept for A/B runs: profiles/r06_inkernel_sums.txt)
+  int col2im_lds;        // HWG_COL2IM_LDS: 0 = col2im_taps on the direct gather kernel (A/B timing, tests), 1 default = the LDS fold where it applies
   int wgrad_reduce_rows; // HWG_WGRAD_REDUCE_ROWS: 0 = tap-at-a-time partial-image reduce (A/B timing), 1 default = row-contiguous stores
   char wino_force[32];   // HWG_WINO_FORCE  "cfg[,nsplit]"
   char wino_bal[32];     // HWG_WINO_BAL    balanced schedule of the 64 x 64 Winograd kernel: -1 never, unset / 0 by model, "G[,lead tiles]" forced

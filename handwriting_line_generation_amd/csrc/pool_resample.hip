@@ -679,7 +679,7 @@ extern "C" int hwg_fused_upsample_weight_bwd_acc(const float* dw4, float* dw3, l
 extern "C" int hwg_col2im_taps(const float* t, float* dx, int N, int H, int W, int P, int Q, int R, int S, int pad_h, int pad_w, int dil_h, int dil_w,
                                void* stream) {
   HWG_REQUIRE(t && dx && N > 0 && H > 0 && W > 0 && P > 0 && Q > 0 && R > 0 && S > 0 && dil_h > 0 && dil_w > 0, "col2im_taps: bad arguments");
-  static const int lds_on = [] { const char* e = getenv("HWG_COL2IM_LDS"); return e && *e ? atoi(e) : 1; }();      // 0: the direct gather (A/B timing)
+  const int lds_on = hwg_tune().col2im_lds;      // HWG_COL2IM_LDS=0: the direct gather (A/B timing); read per tuning epoch like every other knob
   if (lds_on && dil_h == 1 && dil_w == 1 && R == S && (R == 3 || R == 5 || R == 7) && (long long)N * P * Q * R * S < (1ll << 31)) {
     hipStream_t st = (hipStream_t)stream;
     if (R == 3) hipLaunchKernelGGL((col2im_taps_lds_kernel<3, 3, 8, 32>), dim3(hwg_cdiv(W, 32), hwg_cdiv(H, 8), N), dim3(256), 0, st, t, dx, N, H, W, P, Q, pad_h, pad_w);

@@ -908,6 +908,7 @@ def test_pixelnorm(cuda):
 
 
 def test_pools_resample(cuda):
+    # (one toy shape, loose tolerance; every regime against fp64 with derived bounds: tests/test_resample_glue_fp64_gpu.py)
     from handwriting_line_generation_amd import ops
     g = torch.Generator().manual_seed(8)
     x = torch.randn(2, 32, 11, 23, generator=g)
@@ -972,6 +973,7 @@ def test_fused_activation_pools_are_bit_identical_to_the_separate_passes(cuda):
 
 
 def test_cat_onehot_layout(cuda):
+    # (one toy shape, loose tolerance; every regime against fp64 with derived bounds: tests/test_resample_glue_fp64_gpu.py)
     from handwriting_line_generation_amd import ops
     g = torch.Generator().manual_seed(9)
     a = torch.randn(2, 1, 7, 80, generator=g); s = torch.randn(2, 128, generator=g)

@@ -50,3 +50,102 @@ def dump_styles(result, path):
     """the style pickle get_styles.py writes: {"styles": float array [n, style_dim], "authors": [n]}"""
     with open(path, "wb") as f:
         pickle.dump({"styles": result["styles"], "authors": list(result["authors"])}, f)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the model alone over a dataset split (reference get_styles.py:154-255; no trainer, no optimizer)
+def _reset(model):
+    model.pred = model.spaced_label = model.spaced_label_index = None
+
+
+def _batch(inst, gpu):
+    image = inst["image"] if inst["image"].is_cuda else ops.h2d(inst["image"], gpu)
+    label = inst["label"] if inst["label"].is_cuda else ops.h2d(inst["label"], gpu)
+    return image, label
+
+
+def _styles_result(fetches, authors, style_dim):
+    styles = np.concatenate([f.get().numpy() for f in fetches], 0) if fetches else np.zeros((0, style_dim), dtype=np.float32)
+    return {"styles": np.ascontiguousarray(styles, dtype=np.float32), "authors": np.array(authors)}
+
+
+def extract_styles(model, loader, gpu):
+    """-> {"styles": float32 [n, style_dim], "authors": array [n]}: what the reference's get_styles.py pickles for a split - the style
+    model.extract_style gives every line of every batch (all B rows: an author's style once per line of theirs) next to the line's author."""
+    was_training = model.training
+    model.eval()
+    fetches, authors = [], []
+    try:
+        with torch.no_grad():
+            for inst in loader:
+                image, label = _batch(inst, gpu)
+                _reset(model)
+                style = model.extract_style(image, label, inst.get("a_batch_size"))
+                fetches.append(ops.AsyncFetch(style))                # the copy travels while the next batch runs
+                authors += list(inst["author"])
+                _reset(model)
+    finally:
+        _reset(model)
+        if was_training:
+            model.train()
+    return _styles_result(fetches, authors, model.style_dim)
+
+
+def _char_set(config):
+    import json
+    import os
+    char_file = config["data_loader"]["char_file"]
+    if not os.path.exists(char_file):
+        char_file = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data", os.path.basename(char_file))
+    with open(char_file) as f:
+        return {int(k): v for k, v in json.load(f)["idx_to_char"].items()}
+
+
+def eval_split(model, config, loader, gpu):
+    """extract_styles, and on the way the recogniser's error rates on every real line and on the same text rendered in the line's own
+    extracted style, counted on the device (ops.ctc_error_rates; a batch's counts are read while the next batch runs). Adds to
+    extract_styles' result: "lines", per-line lists "cer_real_lines" / "wer_real_lines" / "cer_gen_lines" / "wer_gen_lines" and their means
+    over the lines "cer_real" / "wer_real" / "cer_gen" / "wer_gen"."""
+    idx_to_char = _char_set(config)
+    casesensitive = config.get("trainer", {}).get("casesensitive", True)
+    was_training = model.training
+    model.eval()
+    fetches, authors, handles = [], [], []
+    per_line = {"cer_real": [], "wer_real": [], "cer_gen": [], "wer_gen": []}
+
+    def settle(keep):
+        while len(handles) > keep:
+            real, gen = handles.pop(0)
+            for name, handle in (("real", real), ("gen", gen)):
+                cers, wers, _ = handle.result()
+                per_line["cer_" + name] += cers
+                per_line["wer_" + name] += wers
+    try:
+        with torch.no_grad():
+            for inst in loader:
+                image, label = _batch(inst, gpu)
+                _reset(model)
+                pred = model.hwr(image, None)
+                model.pred = pred
+                style = model.extract_style(image, label, inst.get("a_batch_size"))
+                gen_pred = model.hwr(model(label, inst["label_lengths"], style), None)
+                handles.append((ops.ctc_error_rates(pred, inst["gt"], idx_to_char, casesensitive),
+                                ops.ctc_error_rates(gen_pred, inst["gt"], idx_to_char, casesensitive)))
+                fetches.append(ops.AsyncFetch(style))
+                authors += list(inst["author"])
+                _reset(model)
+                settle(1)
+            settle(0)
+    finally:
+        _reset(model)
+        if was_training:
+            model.train()
+    out = _styles_result(fetches, authors, model.style_dim)
+    out["lines"] = len(per_line["cer_real"])
+    for name, values in per_line.items():
+        total = 0
+        for v in values:
+            total += v
+        out[name] = total / max(len(values), 1)
+        out[name + "_lines"] = values
+    return out

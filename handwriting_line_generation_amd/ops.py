@@ -2382,6 +2382,100 @@ def lines_to_u8(img, widths, out=None, offsets=None):
 
 
 # ----------------------------------------------------------------------------------------------
+# recognition error rates: arg-max, greedy CTC decode, CER / WER counts on the device (csrc/error_rate.hip)
+# ----------------------------------------------------------------------------------------------
+ER_MAX_T, ER_MAX_C, ER_MAX_REF = 8192, 1024, 2047       # the limits hwg_ctc_error_rates checks
+error_rate_fallbacks = 0                                # batches that took the host path (tests read it)
+_error_rate_fallback_said = False
+
+
+class ErrorRatesPending:
+    """kernels already enqueued; `.result()` -> (cer_list, wer_list, pred_strs) per line, waiting (side-stream copy) only for the one
+    int32 buffer that holds the counts and the decoded ids. The divisions are string_utils.rates_from_counts': the host path's values,
+    bit for bit."""
+
+    def __init__(self, fetch, T, refs, idx_to_char, done=None):
+        self.fetch, self.T, self.refs, self.idx_to_char, self.done = fetch, T, refs, idx_to_char, done
+
+    def counts(self):
+        """-> (stats int32 [B, 8], decoded int32 [B, T]) as the kernel left them; None for a batch that took the host path"""
+        if self.fetch is None:
+            return None
+        host = self.fetch.get().numpy()
+        B = len(self.refs)
+        return host[:8 * B].reshape(B, 8), host[8 * B:].reshape(B, self.T)
+
+    def result(self):
+        if self.done is None:
+            from .utils import string_utils
+            stats, decoded = self.counts()
+            stats = stats.tolist()
+            cers, wers, strs = [], [], []
+            for b, ref in enumerate(self.refs):
+                n_dec, cdist, hyp_chars, wdist, hyp_words = stats[b][:5]
+                ref_words = ref.count(string_utils.SPACE) + 1 if ref else 0
+                cers.append(string_utils.rates_from_counts(cdist, len(ref), hyp_chars))
+                wers.append(string_utils.rates_from_counts(wdist, ref_words, hyp_words))
+                strs.append(string_utils.label2str_single(decoded[b, :n_dec].tolist(), self.idx_to_char, False))
+            self.done = (cers, wers, strs)
+        return self.done
+
+
+def host_error_rates(pred, gt, idx_to_char, casesensitive=True):
+    """the host path (HWWithStyleTrainer.getCER line by line) on a [T,B,C] numpy array -> (cer_list, wer_list, pred_strs)"""
+    from .utils import string_utils
+    cers, wers, strs = [], [], []
+    for i, gt_line in enumerate(gt):
+        ids, _ = string_utils.naive_decode(pred[:, i])
+        s = string_utils.label2str_single(ids, idx_to_char, False)
+        cers.append(string_utils.cer(gt_line, s, casesensitive))
+        wers.append(string_utils.wer(gt_line, s, casesensitive))
+        strs.append(s)
+    return cers, wers, strs
+
+
+def ctc_error_rates(pred, gt, idx_to_char, casesensitive=True):
+    """Greedy CTC decode of the recogniser's output `pred` [T,B,C] (device, fp32) and CER / WER of every line against the texts `gt`, on the
+    device: -> ErrorRatesPending. One upload (class table, reference offsets and code points), two launches, one asynchronous fetch. Where
+    the device cannot give string_utils.cer / wer's values - a character set class_code_table refuses, or a size beyond the kernel's limits -
+    the batch takes the host path: same values, said once on stderr."""
+    import numpy as np
+    from .utils import string_utils
+    global error_rate_fallbacks, _error_rate_fallback_said
+    if pred.dim() != 3 or not pred.is_cuda or pred.dtype != torch.float32:
+        raise L.HwgError("ctc_error_rates: pred must be a [T,B,C] fp32 device tensor, got %s %s" % (tuple(pred.shape), pred.dtype))
+    T, B, C = pred.shape
+    if T < 1 or B < 1 or C < 2 or len(gt) != B:
+        raise L.HwgError("ctc_error_rates: %d texts for pred %s" % (len(gt), tuple(pred.shape)))
+    pred = pred.detach().contiguous()
+    table = string_utils.class_code_table(idx_to_char, C, casesensitive)
+    refs = [string_utils.normalise_ref(g, casesensitive) for g in gt]
+    longest = max(len(r) for r in refs)
+    if table is None or T > ER_MAX_T or C > ER_MAX_C or longest > ER_MAX_REF:
+        error_rate_fallbacks += 1
+        if not _error_rate_fallback_said:
+            _error_rate_fallback_said = True
+            import sys
+            why = "the character set does not compare class by class" if table is None else \
+                "T=%d C=%d longest reference %d is beyond the kernel's limits (%d, %d, %d)" % (T, C, longest, ER_MAX_T, ER_MAX_C, ER_MAX_REF)
+            print("ctc_error_rates: %s; such batches are scored on the host" % why, file=sys.stderr)
+        return ErrorRatesPending(None, T, refs, idx_to_char, done=host_error_rates(pred.cpu().numpy(), gt, idx_to_char, casesensitive))
+    offsets = np.zeros(B + 1, dtype=np.int32)
+    np.cumsum([len(r) for r in refs], out=offsets[1:])
+    total = int(offsets[B])
+    packed = np.empty(C + B + 1 + max(total, 1), dtype=np.int32)          # class table, offsets, code points: one upload
+    packed[:C] = table
+    packed[C:C + B + 1] = offsets
+    packed[C + B + 1:] = 0
+    if total:
+        packed[C + B + 1:C + B + 1 + total] = np.fromiter((c for r in refs for c in r), dtype=np.int32, count=total)
+    packed_d = h2d(packed, pred.device)
+    out = torch.empty((8 * B + B * T,), dtype=torch.int32, device=pred.device)
+    L.call("hwg_ctc_error_rates", pred, T, B, C, packed_d, packed_d[C + B + 1:], packed_d[C:C + B + 1], longest, out, _stream())
+    return ErrorRatesPending(AsyncFetch(out), T, refs, idx_to_char)
+
+
+# ----------------------------------------------------------------------------------------------
 # frozen BatchNorm (eval) and the FusedUpsample weight transform
 # ----------------------------------------------------------------------------------------------
 def norm_apply_frozen(x, running_mean, running_var, eps, gamma, beta, act=ACT_NONE, slope=0.0):

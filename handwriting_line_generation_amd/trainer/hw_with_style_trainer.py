@@ -115,6 +115,9 @@ class HWWithStyleTrainer(BaseTrainer):
         # pipelined logging: 0 / False = the reference's behaviour (each iteration returns its own losses: the host drains the GPU every
         # iteration), n >= 1 = iteration i returns the losses of iteration i - n, so the host may run up to n iterations ahead of the GPU
         self.async_log = tr.get("async_log", False)
+        # CER / WER of the logged and the validation batches counted on the device (ops.ctc_error_rates: same values as getCER, fetched with
+        # the losses instead of draining the queue for `pred.cpu()`); off by default = getCER on the host, as the reference
+        self.device_cer = bool(tr.get("device_cer", False))
         # optional: weight-gradient kernels on a second HIP stream (fills the CUs the data-gradient chain leaves idle: +2.7 % steps/s);
         # off by default because co-running kernels inflate the per-kernel durations the roofline measurement relies on
         # "auto": only in the lessons with the long backward passes (auto / auto-gen: three passes over every network), where the GPU is
@@ -449,7 +452,9 @@ class HWWithStyleTrainer(BaseTrainer):
         if flag is not None:
             vals.append(flag.float())
         cer = wer = 0
-        if pred is not None:
+        if pred is not None and self.device_cer:
+            cer = ops.ctc_error_rates(pred, instance["gt"], self.idx_to_char, self.casesensitive)      # resolved with the losses
+        elif pred is not None:
             cer, wer, _ = self.getCER(instance["gt"], pred.detach().cpu().numpy())
         pending = (names, ops.AsyncFetch(torch.cat(vals)) if vals else None, flag is not None, cer, wer)
         if self.async_log:
@@ -461,6 +466,8 @@ class HWWithStyleTrainer(BaseTrainer):
 
     def _resolve_log(self, pending):
         names, fetch, has_flag, cer, wer = pending
+        if isinstance(cer, ops.ErrorRatesPending):
+            cer, wer = self._mean_rates(cer)
         host = fetch.get().tolist() if fetch is not None else []
         if has_flag:
             assert host[-1] == 0.0, "a parameter became NaN/inf"
@@ -701,6 +708,16 @@ class HWWithStyleTrainer(BaseTrainer):
             return cer, wer, pred_strs, all_cer
         return cer, wer, pred_strs
 
+    @staticmethod
+    def _mean_rates(handle):
+        """batch CER and WER of an ops.ctc_error_rates handle, summed and divided as getCER does"""
+        cers, wers, _ = handle.result()
+        cer = wer = 0
+        for c, w in zip(cers, wers):
+            cer += c
+            wer += w
+        return cer / len(cers), wer / len(wers)
+
     def _valid_epoch(self):
         """validation pass (trainer :437-486): the curriculum's validation lesson (or the recogniser step) on every batch of the validation
         loader under no_grad; weighted losses, CER and WER averaged over the batches"""
@@ -708,20 +725,31 @@ class HWWithStyleTrainer(BaseTrainer):
         totals = defaultdict(float)
         total_loss = total_cer = total_wer = 0.0
         n = 0
+        late = None                   # device_cer: a batch's counts are read one batch late, while the next batch is already enqueued
         with torch.no_grad():
             for instance in self.valid_data_loader:
                 if self.curriculum:
                     losses, pred = self.run_gen(instance, self.curriculum.getValid()), None
                 else:
                     pred, losses = self.run_hwr(instance)
+                if pred is not None and self.device_cer:
+                    late, handle = ops.ctc_error_rates(pred, instance["gt"], self.idx_to_char, self.casesensitive), late
+                    if handle is not None:
+                        cer, wer = self._mean_rates(handle)
+                        total_cer += cer
+                        total_wer += wer
                 for name, v in losses.items():
                     w = float(v) * self.lossWeights[name[:-4]]
                     total_loss += w
                     totals["val_" + name] += w
-                if pred is not None:
+                if pred is not None and not self.device_cer:
                     cer, wer, _ = self.getCER(instance["gt"], pred.detach().cpu().numpy())
                     total_cer += cer
                     total_wer += wer
                 n += 1
+            if late is not None:
+                cer, wer = self._mean_rates(late)
+                total_cer += cer
+                total_wer += wer
         n = max(n, 1)
         return {"val_loss": total_loss / n, "val_CER": total_cer / n, "val_WER": total_wer / n, **{k: v / n for k, v in totals.items()}}

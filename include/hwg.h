@@ -521,6 +521,23 @@ int hwg_augment_warp(const float* x, const int* lines_i, const float* lines_f, i
  * ------------------------------------------------------------------------------------------ */
 int hwg_lines_to_u8(const float* img, int B, int H, int W, const int* widths, const long long* offsets, unsigned char* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Recognition error rates on the device (trainer/hw_with_style_trainer.py:894-914 getCER, utils/string_utils.py naive_decode,
+ * utils/error_rates.py:2-26 cer / wer - there on the host, after downloading the whole prediction).
+ * pred [T][B][C] fp32 (the recogniser's output as it stands); class_code [C] int32: the code point class c compares as (32 for every
+ * white-space class, lower-cased for a case-insensitive comparison; entry 0, the blank, is unused); ref_codes / ref_offsets [B+1] int32: the
+ * reference lines as code points, ragged, already white-space normalised (and lower-cased) by the host; max_ref_len: the longest of them.
+ * out int32 [8 * B + B * T]: per line stats[8] = {decoded length, character edit distance, hypothesis characters after white-space
+ * normalisation, word edit distance, hypothesis words, 0, 0, 0}, then decoded [B][T]: the greedy class ids before normalisation
+ * (row b: stats[0] ids, then zeros).
+ * Arg-max as np.argmax (first maximum; a NaN beats every number, the first NaN wins); greedy CTC (class 0 dropped, a class equal to its
+ * predecessor in the raw sequence dropped); hypothesis as " ".join(h.split()); Levenshtein with unit costs over code points, and over words
+ * split at spaces (two words are equal only if all their code points are).
+ * Limits, checked here before any launch: T <= 8192, C <= 1024, max_ref_len <= 2047. Two launches: row arg-max, one wavefront per line.
+ * ------------------------------------------------------------------------------------------ */
+int hwg_ctc_error_rates(const float* pred, int T, int B, int C, const int* class_code, const int* ref_codes, const int* ref_offsets,
+                        int max_ref_len, int* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

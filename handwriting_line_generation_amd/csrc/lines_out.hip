@@ -39,3 +39,71 @@ extern "C" int hwg_lines_to_u8(const float* img, int B, int H, int W, const int*
   HWG_LAUNCH_CHECK("lines_to_u8");
   return HWG_OK;
 }
+
+// ---- the way back: ragged 8-bit lines (the layout above) into a collated fp32 batch, mixed with the rows of a real batch ----------------
+// What HWDataset.__getitem__ and collate do on the host for a line read from disk - 1 - p / 128, padded with -1 to the widest line of the
+// batch - for lines that were generated on this device and never left it. One launch writes EVERY element of out [B,1,H,W]: row b is line
+// select[b] = k >= 0 of the pool (pixels, offsets, widths), or row r of `real` [Br,1,H,Wr] for select[b] = -1 - r.
+//
+// A pool row: one lane owns 4 output columns - one 32-bit load, one 16-byte store; columns >= widths[k] are never read. A real row has an
+// arbitrary Wr (row stride and alignment are no multiples of 4): four scalar loads, one 16-byte store. Every level is exact in fp32
+// (p / 128 is a power-of-two scaling, 1 - q with q a multiple of 2^-7 below 2), so this IS the host's arithmetic.
+//
+// The caller validated the tables; an entry that is bad all the same (k >= n_lines, r >= Br, a line that ends behind pixel_bytes) makes
+// its row padding: nothing is read through it. All stores are inside out [B,1,H,W] whatever the tables hold.
+__global__ __launch_bounds__(LINES_BLOCK) void lines_from_u8_kernel(const unsigned char* __restrict__ pixels, long long pixel_bytes,
+                                                                    const long long* __restrict__ offsets, const int* __restrict__ widths,
+                                                                    int n_lines, const int* __restrict__ select, const float* __restrict__ real,
+                                                                    int Br, int Wr, int H, int W, float* __restrict__ out) {
+  const int b = blockIdx.z, y = blockIdx.y;
+  const int col = 4 * (blockIdx.x * LINES_BLOCK + threadIdx.x);
+  if (col >= W) return;
+  const int s = select[b];
+  f32x4 v = {-1.0f, -1.0f, -1.0f, -1.0f};          // PADDING_CONSTANT
+  if (s >= 0) {
+    if (s < n_lines) {
+      const int w = widths[s];
+      const long long off = offsets[s];
+      const bool ok = w > 0 && w <= W && (w & 3) == 0 && off >= 0 && (off & 3) == 0 && off + (long long)H * w <= pixel_bytes;
+      if (ok && col < w) {
+        const unsigned px = *(const unsigned*)(pixels + off + (size_t)y * w + col);
+        v.x = 1.0f - (float)(px & 255u) / 128.0f;
+        v.y = 1.0f - (float)((px >> 8) & 255u) / 128.0f;
+        v.z = 1.0f - (float)((px >> 16) & 255u) / 128.0f;
+        v.w = 1.0f - (float)(px >> 24) / 128.0f;
+      }
+    }
+  } else {
+    const int r = -1 - s;
+    if (r < Br) {
+      const float* row = real + ((size_t)r * H + y) * Wr;
+      if (col + 0 < Wr) v.x = row[col + 0];
+      if (col + 1 < Wr) v.y = row[col + 1];
+      if (col + 2 < Wr) v.z = row[col + 2];
+      if (col + 3 < Wr) v.w = row[col + 3];
+    }
+  }
+  *(f32x4*)(out + ((size_t)b * H + y) * W + col) = v;
+}
+
+extern "C" int hwg_lines_from_u8(const unsigned char* pixels, long long pixel_bytes, const long long* offsets, const int* widths, int n_lines,
+                                 const int* select, int min_select, const float* real, int Br, int Wr, int B, int H, int W, float* out,
+                                 void* stream) {
+  HWG_REQUIRE(pixels && offsets && widths && select && out, "lines_from_u8: null argument");
+  HWG_REQUIRE(B > 0 && H > 0 && W > 0 && B <= 65535 && H <= 65535, "lines_from_u8: bad sizes B=%d H=%d W=%d", B, H, W);
+  HWG_REQUIRE(n_lines >= 0 && pixel_bytes >= 0, "lines_from_u8: bad sizes n_lines=%d pixel_bytes=%lld", n_lines, pixel_bytes);
+  HWG_REQUIRE(W % 4 == 0, "lines_from_u8: batch width %d is not a multiple of 4", W);
+  HWG_REQUIRE(((uintptr_t)out & 15) == 0 && ((uintptr_t)pixels & 3) == 0, "lines_from_u8: out must be 16-byte aligned and pixels 4-byte aligned");
+  if (real) {
+    HWG_REQUIRE(Br > 0 && Wr > 0 && Wr <= W, "lines_from_u8: bad sizes of the real batch Br=%d Wr=%d (batch width %d)", Br, Wr, W);
+    HWG_REQUIRE(((uintptr_t)real & 3) == 0, "lines_from_u8: real must be 4-byte aligned");
+    HWG_REQUIRE(min_select >= -Br, "lines_from_u8: select entry %d names a row behind the %d of the real batch", min_select, Br);
+  } else {
+    HWG_REQUIRE(min_select >= 0, "lines_from_u8: negative select entry %d without a real batch", min_select);
+    Br = Wr = 0;
+  }
+  hipLaunchKernelGGL(lines_from_u8_kernel, dim3(hwg_cdiv(W / 4, LINES_BLOCK), H, B), dim3(LINES_BLOCK), 0, (hipStream_t)stream, pixels,
+                     pixel_bytes, offsets, widths, n_lines, select, real, Br, Wr, H, W, out);
+  HWG_LAUNCH_CHECK("lines_from_u8");
+  return HWG_OK;
+}

@@ -64,36 +64,43 @@ class DeviceAugment:
         return len(self.loader)
 
     def mesh_for(self, image):
-        from .. import ops
-        B, _, H, _ = image.shape
         x_off, widths = line_extents(image)
+        return self.mesh_from_extents(image.shape[2], x_off, widths)
+
+    def mesh_from_extents(self, H, x_off, widths):
+        """the variant's lattices for lines of height H with these extents (the "low" variant's coin flips: two per line, in line order)"""
+        from .. import ops
         if self.variant == "low":
             bright, warp = [], []
-            for _ in range(B):
+            for _ in range(len(widths)):
                 bright.append(random.random() > 0.1)
                 warp.append(random.random() > 0.01)
             return ops.LineMesh(H, widths, sigma=0.7, x_off=x_off, warp=warp, bright=bright)
         return ops.LineMesh(H, widths, sigma=1.5, x_off=x_off)
 
-    def apply(self, instance):
+    def augment(self, dev_image, mesh):
+        """the uploaded batch `dev_image` [B,1,H,W] re-lit and warped over `mesh` -> a new device tensor (two launches); the draws are the
+        device generator's, or numpy's in host mode"""
         from .. import ops, rng
+        if rng.mode() == "device":
+            return ops.augment_lines(dev_image, mesh, rng=rng.device_rng())
+        fg_bg, disp = [], []
+        for b, src in enumerate(mesh.src):
+            fg_bg.append(np.random.normal(0, ops.AUG_BRIGHT_SIGMA, size=2))
+            if src is None:
+                disp.append(None)
+                continue
+            n = (len(src[0]), len(src[1]))
+            dy = np.random.normal(0.0, mesh.sigma[b], size=n)
+            disp.append((dy, np.random.normal(0.0, mesh.sigma[b], size=n)))
+        mesh.disp = disp
+        return ops.augment_lines(dev_image, mesh, fg_bg=np.asarray(fg_bg))
+
+    def apply(self, instance):
+        from .. import ops
         image = instance["image"]
         mesh = self.mesh_for(image)
-        dev_image = ops.h2d(image, self.device)
-        if rng.mode() == "device":
-            out = ops.augment_lines(dev_image, mesh, rng=rng.device_rng())
-        else:
-            fg_bg, disp = [], []
-            for b, src in enumerate(mesh.src):
-                fg_bg.append(np.random.normal(0, ops.AUG_BRIGHT_SIGMA, size=2))
-                if src is None:
-                    disp.append(None)
-                    continue
-                n = (len(src[0]), len(src[1]))
-                dy = np.random.normal(0.0, mesh.sigma[b], size=n)
-                disp.append((dy, np.random.normal(0.0, mesh.sigma[b], size=n)))
-            mesh.disp = disp
-            out = ops.augment_lines(dev_image, mesh, fg_bg=np.asarray(fg_bg))
+        out = self.augment(ops.h2d(image, self.device), mesh)
         instance = dict(instance)
         instance["image"] = out
         return instance

@@ -265,16 +265,16 @@ def _bucket_requests(texts, styles, char_to_idx, batches, gpu):
         yield torch.from_numpy(label), torch.IntTensor(len(idx)).fill_(n), ops.h2d(style.contiguous(), gpu)
 
 
-def render_lines(model, texts, styles, char_to_idx, gpu, batch_lines=64, skipped=None):
-    """Generator over (index, uint8 numpy [64, w]) for every text, text i in style styles[i] ([n, style_dim], host or device), in any order:
-    the picture the reference writes (generate.py:426), cut to the line's own width.
+def render_lines_device(model, texts, styles, char_to_idx, gpu, batch_lines=64, skipped=None, spacing_noise=False):
+    """Generator over (text indices, pixels, offsets, widths) per bucket, nothing fetched: `pixels` a uint8 1-D DEVICE tensor in which line b
+    of the bucket - text indices[b] in style styles[indices[b]] - is the finished 64 x widths[b] picture pixels[offsets[b]:offsets[b + 1]]
+    (`offsets` host int64 [n + 1], `widths` a host list), the bytes the reference writes (generate.py:426), cut to the line's own width.
 
     Lines are batched BY LABEL LENGTH (bucket_by_length): the spacer convolves over the label axis, and a shorter line's padding labels
     (class 0 one-hot, not zeros) would reach into its last characters; with equal lengths no line sees another's padding, so a line's
     spacing depends on its own text and style only. The batches go through generate_stream; each image is converted and packed ragged on
-    the GPU (ops.lines_to_u8) and fetched on the copy stream while the next batch renders - one fetch in flight. count_std / dup_std are 0
-    for the duration (generate.py:199-200) and restored when the generator ends or is closed. Texts that encode to no label are skipped
-    with a warning (their indices are appended to `skipped` when a list is given)."""
+    the GPU (ops.lines_to_u8). count_std / dup_std are 0 for the duration (generate.py:199-200; `spacing_noise`: the model's values stay)
+    and restored when the generator ends or is closed. Texts that encode to no label are skipped with a warning (their indices are appended to `skipped` when a list is given)."""
     import logging
     styles = torch.as_tensor(styles)
     batches, skip = bucket_by_length(texts, char_to_idx, batch_lines)
@@ -283,23 +283,34 @@ def render_lines(model, texts, styles, char_to_idx, gpu, batch_lines=64, skipped
         if skipped is not None:
             skipped.extend(skip)
     std = (model.count_std, model.dup_std)
-    model.count_std = model.dup_std = 0
+    if not spacing_noise:
+        model.count_std = model.dup_std = 0
     try:
         stream = generate_stream(model, _bucket_requests(texts, styles, char_to_idx, batches, gpu), gpu)
-        pending = None
         for _, idx in batches:
-            with torch.no_grad():           # (not around the yields: a suspended generator would leave the caller's gradients off)
+            with torch.no_grad():           # (not around the yield: a suspended generator would leave the caller's gradients off)
                 image, padded = next(stream)
-            if pending is not None:
-                yield from _cut_lines(*pending)
-            with torch.no_grad():
                 widths = line_widths(padded, image.shape[3])
                 pixels, offsets = ops.lines_to_u8(image, widths)
-                pending = (idx, ops.AsyncFetch(pixels), offsets, widths, image.shape[2])
+            yield idx, pixels, offsets, widths
+    finally:
+        model.count_std, model.dup_std = std
+
+
+def render_lines(model, texts, styles, char_to_idx, gpu, batch_lines=64, skipped=None):
+    """Generator over (index, uint8 numpy [64, w]) for every text, text i in style styles[i] ([n, style_dim], host or device), in any order:
+    render_lines_device's lines on the host. Each bucket is fetched on the copy stream while the next one renders - one fetch in flight."""
+    buckets = render_lines_device(model, texts, styles, char_to_idx, gpu, batch_lines, skipped)
+    try:
+        pending = None
+        for idx, pixels, offsets, widths in buckets:
+            if pending is not None:
+                yield from _cut_lines(*pending)
+            pending = (idx, ops.AsyncFetch(pixels), offsets, widths, model.image_height)
         if pending is not None:
             yield from _cut_lines(*pending)
     finally:
-        model.count_std, model.dup_std = std
+        buckets.close()            # (a consumer that stops early: the stds come back now, not when the inner generator is collected)
 
 
 def _cut_lines(idx, fetch, offsets, widths, height):

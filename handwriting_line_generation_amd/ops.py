@@ -2381,6 +2381,57 @@ def lines_to_u8(img, widths, out=None, offsets=None):
     return out[:total], offsets
 
 
+def lines_from_u8(pixels, offsets, widths, select, real=None, out=None, height=64):
+    """The inverse of lines_to_u8, mixed with a real batch: -> a collated fp32 device batch [B,1,H,W] whose row b is line select[b] = k >= 0
+    of the ragged pool (`pixels` uint8 1-D device tensor, `offsets` / `widths` host arrays: line k is the H x widths[k] picture at
+    pixels[offsets[k]:], the layout lines_to_u8 writes) as 1 - p / 128, padded with -1, or row r of `real` [Br,1,H,Wr] (device fp32, any
+    Wr) for select[b] = -1 - r. H is real's, or `height` without one. W = max(Wr, selected widths) rounded up to a multiple of 4. One launch
+    (hwg_lines_from_u8) writes every element. The host tables are validated here, before anything is uploaded or launched. `out`: a
+    contiguous fp32 device buffer of at least B * H * W elements to write into (16-byte aligned); the returned tensor is a view of it."""
+    import numpy as np
+    if not torch.is_tensor(pixels) or not pixels.is_cuda or pixels.dtype != torch.uint8 or pixels.dim() != 1 or not pixels.is_contiguous():
+        raise L.HwgError("lines_from_u8: pixels must be a contiguous 1-D uint8 device tensor")
+    if pixels.data_ptr() % 4:
+        raise L.HwgError("lines_from_u8: pixels must be 4-byte aligned")
+    H, Br, Wr = int(height), 0, 0
+    if real is not None:
+        if real.dim() != 4 or real.shape[1] != 1 or not real.is_cuda or real.dtype != torch.float32 or real.shape[0] < 1 or real.shape[3] < 1:
+            raise L.HwgError("lines_from_u8: real must be a [Br,1,H,Wr] fp32 device tensor, got %s %s" % (tuple(real.shape), real.dtype))
+        real = real.contiguous()
+        Br, _, H, Wr = real.shape
+    off = np.asarray(offsets, dtype=np.int64).reshape(-1)
+    w = np.asarray(widths, dtype=np.int64).reshape(-1)
+    sel = np.asarray(select, dtype=np.int64).reshape(-1)
+    n, B = w.shape[0], sel.shape[0]
+    if B < 1:
+        raise L.HwgError("lines_from_u8: empty select")
+    if off.shape[0] < n:
+        raise L.HwgError("lines_from_u8: %d offsets for %d widths" % (off.shape[0], n))
+    if ((sel >= n) | (sel < -Br)).any():
+        raise L.HwgError("lines_from_u8: select entries must lie in [%d, %d), got %s" % (-Br, n, sel.tolist()))
+    used = np.unique(sel[sel >= 0])               # only the selected lines are checked and uploaded: the pool may hold thousands
+    uw, uo = w[used], off[used]
+    if ((uw < 4) | (uw % 4 != 0)).any():
+        raise L.HwgError("lines_from_u8: widths must be positive multiples of 4, got %s" % uw.tolist())
+    if ((uo < 0) | (uo % 4 != 0) | (uo + H * uw > pixels.numel())).any():
+        raise L.HwgError("lines_from_u8: offsets must be multiples of 4 with every line inside the %d bytes of pixels, got %s" % (pixels.numel(), uo.tolist()))
+    W = -(-max(Wr, int(uw.max()) if used.size else 0) // 4) * 4
+    if out is None:
+        out = torch.empty((B, 1, H, W), dtype=torch.float32, device=pixels.device)
+    elif (not torch.is_tensor(out) or not out.is_cuda or out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < B * H * W
+          or out.data_ptr() % 16):
+        raise L.HwgError("lines_from_u8: out must be a contiguous 16-byte aligned fp32 device buffer of at least %d elements" % (B * H * W))
+    m = max(int(used.size), 1)
+    table = np.zeros(3 * m + B, dtype=np.int32)   # offsets [m] int64 first (8-byte aligned), then widths [m] and select [B] int32: one upload
+    table[:2 * m].view(np.int64)[:used.size] = uo
+    table[2 * m:2 * m + used.size] = uw
+    table[3 * m:] = np.where(sel >= 0, np.searchsorted(used, sel), sel)      # pool indices renumbered to the uploaded lines
+    table_d = h2d(table, pixels.device)
+    L.call("hwg_lines_from_u8", pixels, pixels.numel(), table_d[:2 * m], table_d[2 * m:3 * m], int(used.size), table_d[3 * m:], int(sel.min()),
+           real, Br, Wr, B, H, W, out, _stream())
+    return out.view(-1)[:B * H * W].view(B, 1, H, W)
+
+
 # ----------------------------------------------------------------------------------------------
 # recognition error rates: arg-max, greedy CTC decode, CER / WER counts on the device (csrc/error_rate.hip)
 # ----------------------------------------------------------------------------------------------

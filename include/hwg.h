@@ -521,6 +521,22 @@ int hwg_augment_warp(const float* x, const int* lines_i, const float* lines_f, i
  * ------------------------------------------------------------------------------------------ */
 int hwg_lines_to_u8(const float* img, int B, int H, int W, const int* widths, const long long* offsets, unsigned char* out, void* stream);
 
+/* The inverse: ragged 8-bit lines in the layout hwg_lines_to_u8 writes -> a collated fp32 batch, mixed with the rows of a real batch
+ * (datasets/hw_dataset.py:21-67 collate over :135 `1 - img / 128` items - there on the host, per line read from disk).
+ * One launch writes every element of out [B][1][H][W]. select [B] int32 (device): select[b] = k >= 0 takes line k of the pool - pixels
+ * (uint8), offsets [n_lines] int64, widths [n_lines] int32, all on the device; row-major H x widths[k] at pixels + offsets[k] - as
+ * out[b][y][x] = 1 - p / 128 for x < widths[k] and -1 (the padding constant) beyond; select[b] = -1 - r copies row r of
+ * real [Br][1][H][Wr] (fp32, any Wr <= W, 4-byte aligned) and writes -1 beyond column Wr. real may be NULL (then Br and Wr are ignored).
+ * Every level is exact in fp32. One 32-bit load (pool row) or four scalar loads (real row) and one 16-byte store per lane; columns >=
+ * widths[k] are never read.
+ * Checked here: no NULL, B, H, W > 0, W % 4 == 0, out 16-byte and pixels 4-byte aligned, Wr <= W, and min_select - the smallest entry of
+ * select as the caller states it (the table itself is a device array) - not below -Br, i.e. not negative without a real batch. The tables
+ * are the caller's to check (ops.lines_from_u8 validates them on the host before the upload); the kernel turns a row whose entry is bad
+ * all the same (k >= n_lines, r >= Br, a width that is no multiple of 4 or above W, a line that ends behind pixel_bytes) into padding
+ * without reading anything through it. */
+int hwg_lines_from_u8(const unsigned char* pixels, long long pixel_bytes, const long long* offsets, const int* widths, int n_lines,
+                      const int* select, int min_select, const float* real, int Br, int Wr, int B, int H, int W, float* out, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Recognition error rates on the device (trainer/hw_with_style_trainer.py:894-914 getCER, utils/string_utils.py naive_decode,
  * utils/error_rates.py:2-26 cer / wer - there on the host, after downloading the whole prediction).

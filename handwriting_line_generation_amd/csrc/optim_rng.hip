@@ -24,7 +24,23 @@ struct MtArgs {
   const int* chunk_tensor;
   const long long* chunk_off;
   int chunk;
+  int sub;      // elements per workgroup: a chunk is cut into gridDim.y pieces of `sub` elements (a multiple of 4), see mt_split
 };
+
+// Workgroups per chunk of the element-wise kernels. The chunk table is shared with mt_abs_sum, whose per-chunk partials fix a summation
+// order, so the chunks stay what they are; a kernel that writes every element from that element alone can cut them freely. One workgroup
+// per 64 Ki-element chunk gave a CU three streaming workgroups at most (~720 of the ~1.7 k table entries are whole chunks, the rest small
+// tensors): too few bytes in flight. Measured on the flagship parameter list (47 M floats), clip_adam / stash / sets-of-2 axpy in us:
+// 1: 387 / 176 / 212, 4: 322 / 134 / 173, 8: 297 / 121 / 162, 16: 268 / 107 / 152 (5 TB/s), 32: 257 / 113 / 151 with the NaN scan and the
+// zero fill back at 1's time (empty workgroups). Non-temporal stores of m / v / p and four pieces per stream in flight changed nothing.
+constexpr int MT_SPLIT = 16;
+__device__ __forceinline__ bool mt_range(const MtArgs& a, int t, long long& off, long long& end) {
+  const long long o = a.chunk_off[blockIdx.x];
+  end = min(o + (long long)a.chunk, a.numel[t]);
+  off = o + (long long)blockIdx.y * a.sub;
+  end = min(end, off + (long long)a.sub);
+  return off < end;
+}
 
 // blockIdx.y = set (hwg_mt_abs_sum_sets: pointer tables [nsets][nt], partials [nsets][nchunks]; one set: the plain call)
 __global__ __launch_bounds__(256) void mt_abs_sum_kernel(MtArgs a, double* out, int nt) {
@@ -142,7 +158,8 @@ __global__ __launch_bounds__(256) void mt_axpy_sets_kernel(MtArgs a, const float
   const float* src[MAXS];     // (indexed by unrolled loops only: registers)
   float c[MAXS];
   bool any = false, al = true;
-  const long long off = a.chunk_off[blockIdx.x];
+  long long off, end;
+  if (!mt_range(a, t, off, end)) return;
 #pragma unroll
   for (int k = 0; k < MAXS; ++k) {
     src[k] = nullptr; c[k] = 0.f;
@@ -156,7 +173,6 @@ __global__ __launch_bounds__(256) void mt_axpy_sets_kernel(MtArgs a, const float
     }
   }
   if (!any) return;
-  const long long end = min(off + (long long)a.chunk, a.numel[t]);
   al = al && ((reinterpret_cast<uintptr_t>(dst + off)) & 15) == 0;
   const long long n4 = al ? (end - off) >> 2 : 0;
   float4* d4 = reinterpret_cast<float4*>(dst + off);
@@ -189,8 +205,8 @@ __global__ __launch_bounds__(256) void mt_unary_kernel(MtArgs a, int op, float c
   float* x = reinterpret_cast<float*>(a.pa[t]);
   if (!x) return;
   float* y = a.pb ? reinterpret_cast<float*>(a.pb[t]) : nullptr;
-  const long long off = a.chunk_off[blockIdx.x];
-  const long long end = min(off + (long long)a.chunk, a.numel[t]);
+  long long off, end;
+  if (!mt_range(a, t, off, end)) return;
   bool bad = false;
   const bool al = ((reinterpret_cast<uintptr_t>(x + off) | (y ? reinterpret_cast<uintptr_t>(y + off) : 0)) & 15) == 0;
   const long long n4 = al ? (end - off) >> 2 : 0;
@@ -297,8 +313,8 @@ __global__ __launch_bounds__(256) void mt_clip_adam_kernel(MtArgs a, const float
   float* g = reinterpret_cast<float*>(a.pb[t]);
   if (!g) return;
   float* p = reinterpret_cast<float*>(a.pa[t]);
-  const long long off = a.chunk_off[blockIdx.x];
-  const long long end = min(off + (long long)a.chunk, a.numel[t]);
+  long long off, end;
+  if (!mt_range(a, t, off, end)) return;
   if (!p) {      // clip only
     const bool al = (reinterpret_cast<uintptr_t>(g + off) & 15) == 0;
     const long long n4 = al ? (end - off) >> 2 : 0;
@@ -433,7 +449,15 @@ MtArgs make_mt(const void* pa, const void* pb, const void* pc, const void* pd, c
   MtArgs a;
   a.pa = (const long long*)pa; a.pb = (const long long*)pb; a.pc = (const long long*)pc; a.pd = (const long long*)pd;
   a.numel = (const long long*)numel; a.chunk_tensor = (const int*)ct; a.chunk_off = (const long long*)co; a.chunk = chunk;
+  a.sub = chunk;
   return a;
+}
+// cuts every chunk into MT_SPLIT workgroups (pieces stay multiples of 4 elements: the 16-byte body / scalar tail split of every element is
+// what it is with one workgroup per chunk); -> gridDim.y. Chunks too small to cut keep one workgroup.
+int mt_split(MtArgs& a) {
+  if (MT_SPLIT <= 1 || a.chunk % (4 * MT_SPLIT) != 0 || a.chunk / MT_SPLIT < 4096) return 1;
+  a.sub = a.chunk / MT_SPLIT;
+  return MT_SPLIT;
 }
 
 }  // namespace
@@ -488,7 +512,8 @@ extern "C" int hwg_mt_axpy_sets(const void* ptrs_dst, const void* ptrs_src, cons
   HWG_REQUIRE(ptrs_dst && ptrs_src && coef && numel && chunk_tensor && chunk_off && nchunks > 0 && chunk > 0 && nt > 0 && nsets > 0 && nsets <= 8,
               "mt_axpy_sets: bad arguments (at most 8 sets)");
   MtArgs a = make_mt(ptrs_dst, ptrs_src, nullptr, nullptr, numel, chunk_tensor, chunk_off, chunk);
-  hipLaunchKernelGGL(mt_axpy_sets_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, a, coef, nsets, nt);
+  const int ns = mt_split(a);
+  hipLaunchKernelGGL(mt_axpy_sets_kernel, dim3(nchunks, ns), dim3(256), 0, (hipStream_t)stream, a, coef, nsets, nt);
   HWG_LAUNCH_CHECK("mt_axpy_sets");
   return HWG_OK;
 }
@@ -497,7 +522,8 @@ extern "C" int hwg_mt_unary(const void* ptrs_a, const void* ptrs_b, int op, floa
   HWG_REQUIRE(ptrs_a && numel && chunk_tensor && chunk_off && nchunks > 0 && chunk > 0 && op >= 0 && op <= 4, "mt_unary: bad arguments");
   HWG_REQUIRE(op != 2 || flag, "mt_unary: nan scan needs a flag");
   MtArgs a = make_mt(ptrs_a, ptrs_b, nullptr, nullptr, numel, chunk_tensor, chunk_off, chunk);
-  hipLaunchKernelGGL(mt_unary_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, a, op, c, flag);
+  const int ns = mt_split(a);
+  hipLaunchKernelGGL(mt_unary_kernel, dim3(nchunks, ns), dim3(256), 0, (hipStream_t)stream, a, op, c, flag);
   HWG_LAUNCH_CHECK("mt_unary");
   return HWG_OK;
 }
@@ -518,7 +544,8 @@ extern "C" int hwg_mt_clip_adam(const void* ptrs_p, const void* ptrs_g, const vo
   HWG_REQUIRE(ptrs_p && ptrs_g && ptrs_m && ptrs_v && step_size && bc2_sqrt && numel && chunk_tensor && chunk_off && nchunks > 0 && chunk > 0 && clip > 0.f,
               "mt_clip_adam: bad arguments");
   MtArgs a = make_mt(ptrs_p, ptrs_g, ptrs_m, ptrs_v, numel, chunk_tensor, chunk_off, chunk);
-  hipLaunchKernelGGL(mt_clip_adam_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, a, step_size, bc2_sqrt, beta1, beta2, eps, clip, flag);
+  const int ns = mt_split(a);
+  hipLaunchKernelGGL(mt_clip_adam_kernel, dim3(nchunks, ns), dim3(256), 0, (hipStream_t)stream, a, step_size, bc2_sqrt, beta1, beta2, eps, clip, flag);
   HWG_LAUNCH_CHECK("mt_clip_adam");
   return HWG_OK;
 }

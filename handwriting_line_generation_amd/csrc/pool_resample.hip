@@ -1,5 +1,5 @@
 // Pooling / resampling / padding / concatenation kernels on NHWC tensors. All HBM-bound; every kernel is
-// a grid-stride loop over output vectors of V channels (V = 4 when C % 4 == 0, else 1).
+// a grid-stride loop over output vectors of V channels (V = 4 when C % 4 == 0, else 1; max-pool backward also 2).
 #include "hwg_common.h"
 
 namespace {
@@ -157,29 +157,90 @@ __global__ void maxpool_fwd_kernel(const float* x, float* y, int* idx, int N, in
     for (int e = 0; e < V; ++e) idx[(size_t)i * V + e] = bi[e];
   }
 }
+// Backward. NV channels per thread (4, 2 when C is only even, else 1), moved with one 16 / 8 / 4-byte access. Every dx element is 0 + g for one
+// covering window that chose it, (0 + a) + b in ascending (p,q) for two: a routed -0.0 becomes +0.0, as in ATen's max_pool2d backward.
+template <int NV> struct PoolVec { float f[NV]; int i[NV]; };
+template <int NV> __device__ __forceinline__ void pool_load(const float* p, float* r) {
+  if (NV == 4) { const float4 t = *reinterpret_cast<const float4*>(p); r[0] = t.x; r[1 % NV] = t.y; r[2 % NV] = t.z; r[3 % NV] = t.w; }
+  else if (NV == 2) { const float2 t = *reinterpret_cast<const float2*>(p); r[0] = t.x; r[1 % NV] = t.y; }
+  else r[0] = p[0];
+}
+template <int NV> __device__ __forceinline__ void pool_load(const int* p, int* r) {
+  if (NV == 4) { const int4 t = *reinterpret_cast<const int4*>(p); r[0] = t.x; r[1 % NV] = t.y; r[2 % NV] = t.z; r[3 % NV] = t.w; }
+  else if (NV == 2) { const int2 t = *reinterpret_cast<const int2*>(p); r[0] = t.x; r[1 % NV] = t.y; }
+  else r[0] = p[0];
+}
+template <int NV> __device__ __forceinline__ void pool_store(float* p, const float* r) {
+  if (NV == 4) *reinterpret_cast<float4*>(p) = make_float4(r[0], r[1 % NV], r[2 % NV], r[3 % NV]);
+  else if (NV == 2) *reinterpret_cast<float2*>(p) = make_float2(r[0], r[1 % NV]);
+  else p[0] = r[0];
+}
+// gated gradients and arg-max of one pooled vector
+template <int NV, bool RELU>
+__device__ __forceinline__ PoolVec<NV> pool_window(const float* dy, const float* y, const int* idx, long long o) {
+  PoolVec<NV> r;
+  pool_load<NV>(dy + o, r.f);
+  pool_load<NV>(idx + o, r.i);
+  if (RELU) {
+    float yy[NV];
+    pool_load<NV>(y + o, yy);
+    for (int e = 0; e < NV; ++e) r.f[e] = __fmul_rn(r.f[e], yy[e] > 0.f ? 1.f : 0.f);
+  }
+  return r;
+}
+
+// Windows that do not overlap (stride == kernel, no padding): window-major. One thread per pooled vector reads dy / y / idx once and writes
+// the kh*kw input vectors of its window (full resolution is only written, the pooled tensors are read once instead of kh*kw times); the
+// windows of the last pooled row / column also write the zeros of the input rows / columns that no window covers (H % kh, W % kw).
 template <int V, bool RELU>
-__global__ void maxpool_bwd_kernel(const float* dy, const float* y, const int* idx, float* dx, int N, int H, int W, int C, int kh, int kw, int sh, int sw,
-                                   int ph, int pw, int P, int Q) {
+__global__ __launch_bounds__(256) void maxpool_bwd_win_kernel(const float* __restrict__ dy, const float* __restrict__ y, const int* __restrict__ idx,
+                                                              float* __restrict__ dx, int N, int H, int W, int C, int kh, int kw, int P, int Q) {
   const int CV = C / V;
-  const long long total = (long long)N * H * W * CV;
+  const long long total = (long long)N * P * Q * CV;
   GRID_STRIDE(i, total) {
     const int c = (int)(i % CV) * V; unsigned t = i / CV;
-    const int w = (int)(t % W); t /= W;
-    const int h = (int)(t % H); const int n = (int)(t / H);
-    const int me = h * W + w;
-    VecT<V> acc = vzero<V>();
-    // output rows p with p*sh-ph <= h <= p*sh-ph+kh-1
+    const int q = (int)(t % Q); t /= Q;
+    const int p = (int)(t % P); const int n = (int)(t / P);
+    const PoolVec<V> g = pool_window<V, RELU>(dy, y, idx, (long long)i * V);
+    const int hend = p == P - 1 ? H : (p + 1) * kh;      // (rows / columns past the window: uncovered, zero)
+    const int wend = q == Q - 1 ? W : (q + 1) * kw;
+    for (int h = p * kh; h < hend; ++h)
+      for (int w = q * kw; w < wend; ++w) {
+        const int me = h * W + w;
+        float r[V];
+        for (int e = 0; e < V; ++e) { r[e] = 0.f; if (g.i[e] == me) r[e] += g.f[e]; }
+        pool_store<V>(dx + (((long long)n * H + h) * W + w) * C + c, r);
+      }
+  }
+}
+
+// Overlapping / padded windows: a gather over the covering windows, one input row (n,h) per blockIdx.y (its covering pooled rows are decoded
+// once, wave-uniform), the pooled tensors read with vector loads
+template <int V, bool RELU>
+__global__ __launch_bounds__(256) void maxpool_bwd_gather_kernel(const float* __restrict__ dy, const float* __restrict__ y, const int* __restrict__ idx,
+                                                                 float* __restrict__ dx, int N, int H, int W, int C, int kh, int kw, int sh, int sw,
+                                                                 int ph, int pw, int P, int Q) {
+  const int CV = C / V;
+  const unsigned rowv = (unsigned)W * CV;
+  for (unsigned row = blockIdx.y; row < (unsigned)N * H; row += gridDim.y) {
+    const int n = (int)(row / H), h = (int)(row % H);
     int pmin = (h + ph - kh + 1 + sh - 1); pmin = pmin > 0 ? pmin / sh : 0;
     int pmax = (h + ph) / sh; if (pmax > P - 1) pmax = P - 1;
-    int qmin = (w + pw - kw + 1 + sw - 1); qmin = qmin > 0 ? qmin / sw : 0;
-    int qmax = (w + pw) / sw; if (qmax > Q - 1) qmax = Q - 1;
-    for (int p = pmin; p <= pmax; ++p)
-      for (int q = qmin; q <= qmax; ++q) {
-        const long long o = (((long long)n * P + p) * Q + q) * C + c;
-        for (int e = 0; e < V; ++e)
-          if (idx[o + e] == me) acc.v[e] += RELU ? __fmul_rn(dy[o + e], y[o + e] > 0.f ? 1.f : 0.f) : dy[o + e];
-      }
-    vstore<V>(dx + (size_t)i * V, acc);
+    GRID_STRIDE(j, rowv) {
+      const int w = (int)(j / CV), c = (int)(j % CV) * V;
+      const int me = h * W + w;
+      int qmin = (w + pw - kw + 1 + sw - 1); qmin = qmin > 0 ? qmin / sw : 0;
+      int qmax = (w + pw) / sw; if (qmax > Q - 1) qmax = Q - 1;
+      float acc[V];
+      for (int e = 0; e < V; ++e) acc[e] = 0.f;
+      for (int p = pmin; p <= pmax; ++p)
+        for (int q = qmin; q <= qmax; ++q) {
+          const PoolVec<V> g = pool_window<V, RELU>(dy, y, idx, (((long long)n * P + p) * Q + q) * C + c);
+          for (int e = 0; e < V; ++e)
+            if (g.i[e] == me) acc[e] += g.f[e];
+        }
+      pool_store<V>(dx + ((long long)row * W + w) * C + c, acc);
+    }
   }
 }
 
@@ -542,19 +603,41 @@ extern "C" int hwg_maxpool_relu_fwd(const float* x, float* y, int* idx, int N, i
   HWG_LAUNCH_CHECK("maxpool_relu_fwd");
   return HWG_OK;
 }
+template <bool RELU>
+static void launch_maxpool_bwd(const float* dy, const float* y, const int* idx, float* dx, int N, int H, int W, int C, int kh, int kw, int sh, int sw,
+                               int ph, int pw, int P, int Q, hipStream_t st) {
+  const int V = C % 4 == 0 ? 4 : C % 2 == 0 ? 2 : 1;
+  if (sh == kh && sw == kw && ph == 0 && pw == 0 && P == H / kh && Q == W / kw) {
+    const dim3 grid(hwg_stream_grid((long long)N * P * Q * (C / V), 256));
+#define HWG_POOL_WIN(v) hipLaunchKernelGGL((maxpool_bwd_win_kernel<v, RELU>), grid, dim3(256), 0, st, dy, y, idx, dx, N, H, W, C, kh, kw, P, Q)
+    if (V == 4) HWG_POOL_WIN(4); else if (V == 2) HWG_POOL_WIN(2); else HWG_POOL_WIN(1);
+#undef HWG_POOL_WIN
+  } else {
+    const int gx = hwg_stream_grid((long long)W * (C / V), 256);
+    const long long rows = (long long)N * H;
+    const long long gy = rows < 4096 / gx ? rows : (4096 / gx > 0 ? 4096 / gx : 1);
+    const dim3 grid(gx, (unsigned)gy);
+#define HWG_POOL_GATHER(v) \
+  hipLaunchKernelGGL((maxpool_bwd_gather_kernel<v, RELU>), grid, dim3(256), 0, st, dy, y, idx, dx, N, H, W, C, kh, kw, sh, sw, ph, pw, P, Q)
+    if (V == 4) HWG_POOL_GATHER(4); else if (V == 2) HWG_POOL_GATHER(2); else HWG_POOL_GATHER(1);
+#undef HWG_POOL_GATHER
+  }
+}
 extern "C" int hwg_maxpool_bwd(const float* dy, const int* idx, float* dx, int N, int H, int W, int C, int kh, int kw, int sh, int sw, int ph,
                                int pw, int P, int Q, void* stream) {
-  HWG_REQUIRE(dy && dx && idx && N > 0 && C > 0 && P > 0 && Q > 0, "maxpool_bwd: bad arguments");
-  hipStream_t st = (hipStream_t)stream;
-  LAUNCH_V2(maxpool_bwd_kernel, false, (long long)N * H * W * C, C, dy, (const float*)nullptr, idx, dx, N, H, W, C, kh, kw, sh, sw, ph, pw, P, Q);
+  HWG_REQUIRE(dy && dx && idx && N > 0 && H > 0 && W > 0 && C > 0 && P > 0 && Q > 0 && kh > 0 && kw > 0 && sh > 0 && sw > 0 && ph >= 0 && pw >= 0,
+              "maxpool_bwd: bad arguments");
+  HWG_REQUIRE((long long)N * H * W * C < (1ll << 31), "tensor too large for the 32-bit indices of the resampling kernels");
+  launch_maxpool_bwd<false>(dy, nullptr, idx, dx, N, H, W, C, kh, kw, sh, sw, ph, pw, P, Q, (hipStream_t)stream);
   HWG_LAUNCH_CHECK("maxpool_bwd");
   return HWG_OK;
 }
 extern "C" int hwg_maxpool_relu_bwd(const float* dy, const float* y, const int* idx, float* dx, int N, int H, int W, int C, int kh, int kw, int sh, int sw,
                                     int ph, int pw, int P, int Q, void* stream) {
-  HWG_REQUIRE(dy && y && dx && idx && N > 0 && C > 0 && P > 0 && Q > 0, "maxpool_relu_bwd: bad arguments");
-  hipStream_t st = (hipStream_t)stream;
-  LAUNCH_V2(maxpool_bwd_kernel, true, (long long)N * H * W * C, C, dy, y, idx, dx, N, H, W, C, kh, kw, sh, sw, ph, pw, P, Q);
+  HWG_REQUIRE(dy && y && dx && idx && N > 0 && H > 0 && W > 0 && C > 0 && P > 0 && Q > 0 && kh > 0 && kw > 0 && sh > 0 && sw > 0 && ph >= 0 && pw >= 0,
+              "maxpool_relu_bwd: bad arguments");
+  HWG_REQUIRE((long long)N * H * W * C < (1ll << 31), "tensor too large for the 32-bit indices of the resampling kernels");
+  launch_maxpool_bwd<true>(dy, y, idx, dx, N, H, W, C, kh, kw, sh, sw, ph, pw, P, Q, (hipStream_t)stream);
   HWG_LAUNCH_CHECK("maxpool_relu_bwd");
   return HWG_OK;
 }

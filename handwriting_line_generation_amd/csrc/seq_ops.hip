@@ -49,10 +49,9 @@ __device__ __forceinline__ int ctc_ext(const int* tg, int s) { return (s & 1) ? 
 
 // one block per batch item. lp: [T][B][C]; targets: [B][Lmax] int32; writes log_alpha [B][T][2*Lmax+1] and nll[B]. The recursion's rows
 // live in LDS (a chain of T dependent steps: one barrier each, no global-memory round trip); global log_alpha is written for the backward pass
-__global__ __launch_bounds__(256) void ctc_alpha_kernel(const float* lp, const int* targets, const int* in_len, const int* tg_len, int T, int B,
-                                                        int C, int Lmax, float* log_alpha, float* nll) {
-  extern __shared__ float rows[];      // [2][NSmax] alpha rows, then NSmax ints: extended target
-  const int b = blockIdx.x;
+__device__ __forceinline__ void ctc_alpha_body(float* rows /* [2][NSmax] alpha rows, then NSmax ints: extended target */, int b, const float* lp,
+                                               const int* targets, const int* in_len, const int* tg_len, int T, int B, int C, int Lmax,
+                                               float* log_alpha, float* nll) {
   const int S = tg_len[b];
   const int Tb = in_len[b];
   const int NS = 2 * S + 1;
@@ -107,6 +106,11 @@ __global__ __launch_bounds__(256) void ctc_alpha_kernel(const float* lp, const i
     nll[b] = r;
   }
 }
+__global__ __launch_bounds__(256) void ctc_alpha_kernel(const float* lp, const int* targets, const int* in_len, const int* tg_len, int T, int B,
+                                                        int C, int Lmax, float* log_alpha, float* nll) {
+  extern __shared__ float rows[];
+  ctc_alpha_body(rows, blockIdx.x, lp, targets, in_len, tg_len, T, B, C, Lmax, log_alpha, nll);
+}
 // loss = mean_b( nll_b / max(tg_len_b, 1) ); a non-finite mean is reported as 0 (model/loss.py:28-30)
 __global__ void ctc_mean_kernel(const float* nll, const int* tg_len, int B, float* loss, int* finite_flag) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
@@ -120,10 +124,9 @@ __global__ void ctc_mean_kernel(const float* nll, const int* tg_len, int B, floa
 }
 // backward, part 1: beta recursion (eq. 10-11 of Graves et al., as ATen's ctc_loss_backward_cpu), one block per batch item, rows kept in LDS
 // (the recursion is a chain of T dependent steps: a global-memory round trip per step would cost more than the arithmetic); log_beta [B][T][NSmax]
-__global__ __launch_bounds__(256) void ctc_beta_kernel(const float* lp, const int* targets, const int* in_len, const int* tg_len, int T, int B,
-                                                       int C, int Lmax, float* log_beta) {
-  extern __shared__ float rows[];      // [2][NSmax] beta rows, then NSmax ints: extended target
-  const int b = blockIdx.x;
+__device__ __forceinline__ void ctc_beta_body(float* rows /* [2][NSmax] beta rows, then NSmax ints: extended target */, int b, const float* lp,
+                                              const int* targets, const int* in_len, const int* tg_len, int T, int B, int C, int Lmax,
+                                              float* log_beta) {
   const int S = tg_len[b];
   const int Tb = in_len[b];
   const int NS = 2 * S + 1;
@@ -160,6 +163,20 @@ __global__ __launch_bounds__(256) void ctc_beta_kernel(const float* lp, const in
     }
     __syncthreads();
   }
+}
+__global__ __launch_bounds__(256) void ctc_beta_kernel(const float* lp, const int* targets, const int* in_len, const int* tg_len, int T, int B,
+                                                       int C, int Lmax, float* log_beta) {
+  extern __shared__ float rows[];
+  ctc_beta_body(rows, blockIdx.x, lp, targets, in_len, tg_len, T, B, C, Lmax, log_beta);
+}
+// Both recursions in one launch: blocks 0..B-1 run alpha, blocks B..2B-1 run beta. Beta reads log_probs only (not the incoming gradient) and
+// each recursion is one latency-bound workgroup per line, so the two chains run side by side on different CUs and the backward pass starts
+// at ctc_grad_kernel. Same bodies as the two kernels above.
+__global__ __launch_bounds__(256) void ctc_alpha_beta_kernel(const float* lp, const int* targets, const int* in_len, const int* tg_len, int T, int B,
+                                                             int C, int Lmax, float* log_alpha, float* nll, float* log_beta) {
+  extern __shared__ float rows[];
+  if ((int)blockIdx.x < B) ctc_alpha_body(rows, blockIdx.x, lp, targets, in_len, tg_len, T, B, C, Lmax, log_alpha, nll);
+  else ctc_beta_body(rows, blockIdx.x - B, lp, targets, in_len, tg_len, T, B, C, Lmax, log_beta);
 }
 
 // backward, part 2: gradient wrt log-probs (eq. 16), one block per (t, b) - every (t, b, class) is independent once alpha and beta exist.
@@ -324,8 +341,8 @@ extern "C" size_t hwg_ctc_workspace(int T, int B, int Lmax) {
   // log_alpha [B][T][NS] + log_beta [B][T][NS] + nll[B] + flag
   return (2 * (size_t)B * T * NS + B + 4) * sizeof(float);
 }
-extern "C" int hwg_ctc_fwd(const float* log_probs, const int* targets, const int* input_lengths, const int* target_lengths, int T, int B, int C,
-                           int Lmax, float* loss, void* ws, size_t ws_bytes, void* stream) {
+static int ctc_fwd(const float* log_probs, const int* targets, const int* input_lengths, const int* target_lengths, int T, int B, int C, int Lmax,
+                   float* loss, void* ws, size_t ws_bytes, void* stream, bool with_beta) {
   HWG_REQUIRE(log_probs && targets && input_lengths && target_lengths && loss && T > 0 && B > 0 && C > 0 && Lmax > 0, "ctc_fwd: bad arguments");
   if (!ws || ws_bytes < hwg_ctc_workspace(T, B, Lmax)) { hwg_set_error("ctc_fwd: workspace too small"); return HWG_ERR_WORKSPACE; }
   hipStream_t st = (hipStream_t)stream;
@@ -334,14 +351,26 @@ extern "C" int hwg_ctc_fwd(const float* log_probs, const int* targets, const int
   float* lb = la + (size_t)B * T * NS;
   float* nll = lb + (size_t)B * T * NS;
   int* flag = (int*)(nll + B);
-  hipLaunchKernelGGL(ctc_alpha_kernel, dim3(B), dim3(256), 3 * NS * sizeof(float), st, log_probs, targets, input_lengths, target_lengths, T, B, C, Lmax, la, nll);
+  if (with_beta)
+    hipLaunchKernelGGL(ctc_alpha_beta_kernel, dim3(2 * B), dim3(256), 3 * NS * sizeof(float), st, log_probs, targets, input_lengths, target_lengths, T, B, C,
+                       Lmax, la, nll, lb);
+  else
+    hipLaunchKernelGGL(ctc_alpha_kernel, dim3(B), dim3(256), 3 * NS * sizeof(float), st, log_probs, targets, input_lengths, target_lengths, T, B, C, Lmax, la, nll);
   HWG_LAUNCH_CHECK("ctc_alpha");
   hipLaunchKernelGGL(ctc_mean_kernel, dim3(1), dim3(64), 0, st, (const float*)nll, target_lengths, B, loss, flag);
   HWG_LAUNCH_CHECK("ctc_mean");
   return HWG_OK;
 }
-extern "C" int hwg_ctc_bwd(const float* log_probs, const int* targets, const int* input_lengths, const int* target_lengths, int T, int B, int C,
-                           int Lmax, const float* grad_out, float* grad, void* ws, size_t ws_bytes, void* stream) {
+extern "C" int hwg_ctc_fwd(const float* log_probs, const int* targets, const int* input_lengths, const int* target_lengths, int T, int B, int C,
+                           int Lmax, float* loss, void* ws, size_t ws_bytes, void* stream) {
+  return ctc_fwd(log_probs, targets, input_lengths, target_lengths, T, B, C, Lmax, loss, ws, ws_bytes, stream, false);
+}
+extern "C" int hwg_ctc_fwd_beta(const float* log_probs, const int* targets, const int* input_lengths, const int* target_lengths, int T, int B, int C,
+                                int Lmax, float* loss, void* ws, size_t ws_bytes, void* stream) {
+  return ctc_fwd(log_probs, targets, input_lengths, target_lengths, T, B, C, Lmax, loss, ws, ws_bytes, stream, true);
+}
+static int ctc_bwd(const float* log_probs, const int* targets, const int* input_lengths, const int* target_lengths, int T, int B, int C, int Lmax,
+                   const float* grad_out, float* grad, void* ws, size_t ws_bytes, void* stream, bool have_beta) {
   HWG_REQUIRE(log_probs && targets && input_lengths && target_lengths && grad_out && grad, "ctc_bwd: bad arguments");
   if (!ws || ws_bytes < hwg_ctc_workspace(T, B, Lmax)) { hwg_set_error("ctc_bwd: workspace too small"); return HWG_ERR_WORKSPACE; }
   hipStream_t st = (hipStream_t)stream;
@@ -351,12 +380,22 @@ extern "C" int hwg_ctc_bwd(const float* log_probs, const int* targets, const int
   float* nll = lb + (size_t)B * T * NS;
   int* flag = (int*)(nll + B);
   const size_t lds = (2 * NS + NS) * sizeof(float);
-  hipLaunchKernelGGL(ctc_beta_kernel, dim3(B), dim3(256), lds, st, log_probs, targets, input_lengths, target_lengths, T, B, C, Lmax, lb);
-  HWG_LAUNCH_CHECK("ctc_beta");
+  if (!have_beta) {
+    hipLaunchKernelGGL(ctc_beta_kernel, dim3(B), dim3(256), lds, st, log_probs, targets, input_lengths, target_lengths, T, B, C, Lmax, lb);
+    HWG_LAUNCH_CHECK("ctc_beta");
+  }
   hipLaunchKernelGGL(ctc_grad_kernel, dim3(T, B), dim3(128), 2 * NS * sizeof(float), st, log_probs, targets, input_lengths, target_lengths, T, B, C,
                      Lmax, (const float*)la, (const float*)lb, (const float*)nll, grad_out, (const int*)flag, grad);
   HWG_LAUNCH_CHECK("ctc_grad");
   return HWG_OK;
+}
+extern "C" int hwg_ctc_bwd(const float* log_probs, const int* targets, const int* input_lengths, const int* target_lengths, int T, int B, int C,
+                           int Lmax, const float* grad_out, float* grad, void* ws, size_t ws_bytes, void* stream) {
+  return ctc_bwd(log_probs, targets, input_lengths, target_lengths, T, B, C, Lmax, grad_out, grad, ws, ws_bytes, stream, false);
+}
+extern "C" int hwg_ctc_bwd_grad(const float* log_probs, const int* targets, const int* input_lengths, const int* target_lengths, int T, int B, int C,
+                                int Lmax, const float* grad_out, float* grad, void* ws, size_t ws_bytes, void* stream) {
+  return ctc_bwd(log_probs, targets, input_lengths, target_lengths, T, B, C, Lmax, grad_out, grad, ws, ws_bytes, stream, true);
 }
 
 extern "C" size_t hwg_dtw_workspace(int T, int B, int L) {

@@ -1826,6 +1826,11 @@ def log_softmax_tbc(x):
     return _LogSoftmaxTB.apply(x)
 
 
+# The beta recursion of the CTC backward pass reads log_probs only, so the forward launch runs it beside alpha (hwg_ctc_fwd_beta) whenever a
+# gradient will be asked for, and backward starts at the gradient kernel. False: beta in its own launch at the head of backward (same bits).
+CTC_BETA_IN_FWD = True
+
+
 class _CTC(Function):
     @staticmethod
     def forward(ctx, log_probs, targets, in_len, tg_len):
@@ -1837,7 +1842,9 @@ class _CTC(Function):
         nbytes = L.query("hwg_ctc_workspace", T, B, Lmax)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=log_probs.device)  # kept for backward
         loss = torch.empty((), dtype=torch.float32, device=log_probs.device)
-        L.call("hwg_ctc_fwd", log_probs, targets, in_len, tg_len, T, B, C, Lmax, loss, ws, ws.numel(), _stream())
+        ctx.have_beta = CTC_BETA_IN_FWD and ctx.needs_input_grad[0]
+        L.call("hwg_ctc_fwd_beta" if ctx.have_beta else "hwg_ctc_fwd", log_probs, targets, in_len, tg_len, T, B, C, Lmax, loss, ws, ws.numel(),
+               _stream())
         ctx.save_for_backward(log_probs, targets, in_len, tg_len, ws)
         return loss
 
@@ -1846,7 +1853,8 @@ class _CTC(Function):
         log_probs, targets, in_len, tg_len, ws = ctx.saved_tensors
         T, B, C = log_probs.shape
         grad = torch.empty_like(log_probs)
-        L.call("hwg_ctc_bwd", log_probs, targets, in_len, tg_len, T, B, C, targets.shape[1], gout.contiguous(), grad, ws, ws.numel(), _stream())
+        L.call("hwg_ctc_bwd_grad" if ctx.have_beta else "hwg_ctc_bwd", log_probs, targets, in_len, tg_len, T, B, C, targets.shape[1],
+               gout.contiguous(), grad, ws, ws.numel(), _stream())
         return grad, None, None, None
 
 

@@ -325,6 +325,12 @@ int hwg_ctc_fwd(const float* log_probs, const int* targets, const int* input_len
                 int Lmax, float* loss, void* ws, size_t ws_bytes, void* stream);
 int hwg_ctc_bwd(const float* log_probs, const int* targets, const int* input_lengths, const int* target_lengths, int T, int B, int C,
                 int Lmax, const float* grad_out, float* grad, void* ws, size_t ws_bytes, void* stream);
+/* the same pair with the beta recursion moved into the forward launch (it needs log_probs only; blocks B..2B-1 run it beside alpha):
+ * hwg_ctc_bwd_grad starts at the gradient kernel and must follow hwg_ctc_fwd_beta on the same workspace. Same bits as the pair above. */
+int hwg_ctc_fwd_beta(const float* log_probs, const int* targets, const int* input_lengths, const int* target_lengths, int T, int B, int C,
+                     int Lmax, float* loss, void* ws, size_t ws_bytes, void* stream);
+int hwg_ctc_bwd_grad(const float* log_probs, const int* targets, const int* input_lengths, const int* target_lengths, int T, int B, int C,
+                     int Lmax, const float* grad_out, float* grad, void* ws, size_t ws_bytes, void* stream);
 /* pred [T][B][C] log-probs, label [L][B] int32 -> out int64 [T+2L+1][B] zero padded, lens[B] path lengths (bit exact) */
 size_t hwg_dtw_workspace(int T, int B, int L);
 int hwg_dtw_align(const float* pred, const int* label, int T, int B, int C, int L, long long* out, int* lens, void* ws, size_t ws_bytes,

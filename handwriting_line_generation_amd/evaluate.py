@@ -149,3 +149,65 @@ def eval_split(model, config, loader, gpu):
         out[name] = total / max(len(values), 1)
         out[name + "_lines"] = values
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# writer retrieval over a style file (reference eval_writer_id.py: is the nearest style to a line's style a line of the same writer?)
+def author_ids(authors):
+    """-> (int32 [n] ids, number of writers): equal authors (Python equality, as the reference's `author1 == author2`) get equal ids,
+    numbered in order of first appearance"""
+    table = {}
+    ids = np.empty(len(authors), dtype=np.int32)
+    for i, a in enumerate(authors):
+        a = a.item() if isinstance(a, np.generic) else a
+        ids[i] = table.setdefault(a, len(table))
+    return ids, len(table)
+
+
+def dedupe_rows(styles, ids):
+    """-> bool [n]: False for a row whose writer and whose style, byte for byte, are those of the row directly above it (extract_styles
+    writes a writer's style once per line of theirs)"""
+    keep = np.ones(len(ids), dtype=bool)
+    if len(ids) > 1:
+        raw = np.ascontiguousarray(styles).view(np.uint8).reshape(len(ids), -1)
+        keep[1:] = ~((ids[1:] == ids[:-1]) & (raw[1:] == raw[:-1]).all(axis=1))
+    return keep
+
+
+def writer_id(styles, authors, gpu, tops=(1, 5, 20), dedupe=False):
+    """Writer retrieval accuracy of a style space: styles numpy [n, D] or [n, D, 1, 1], authors a sequence of n. Per row the columns are
+    ordered by distance (stable: ties keep column order, the row's own column included); first_rank is the first place >= 1 that holds a
+    line of the row's writer, top-k the share of rows with first_rank <= min(k, n - 1). ->
+    {"lines", "dim", "writers", "l1": {...}, "l2": {...}} with {"top<k>" for k in tops, "mean_first_rank" (over the rows that have one;
+    None if no row has), "rows_without_match"} per metric (l1: sum |a - b|, l2: sum (a - b)^2, fp32); with dedupe also "dropped": rows
+    removed beforehand because writer and style repeat the row above. Distances and ranks are computed on the device
+    (ops.writer_first_rank); nothing of size n x n is stored."""
+    styles = np.asarray(styles)
+    if styles.ndim == 4 and styles.shape[2:] == (1, 1):
+        styles = styles[:, :, 0, 0]
+    if styles.ndim != 2 or styles.shape[0] < 1 or styles.shape[1] < 1:
+        raise ValueError("writer_id: styles must be [n, D] or [n, D, 1, 1] with n, D >= 1, got %s" % (tuple(styles.shape),))
+    styles = np.ascontiguousarray(styles, dtype=np.float32)
+    if len(authors) != styles.shape[0]:
+        raise ValueError("writer_id: %d authors for %d styles" % (len(authors), styles.shape[0]))
+    finite = np.isfinite(styles).all(axis=1)
+    if not finite.all():
+        raise ValueError("writer_id: style row %d is not finite (an order with NaN is not defined)" % int(np.argmin(finite)))
+    ids, _ = author_ids(authors)
+    out = {}
+    if dedupe:
+        keep = dedupe_rows(styles, ids)
+        out["dropped"] = int((~keep).sum())
+        styles, ids = np.ascontiguousarray(styles[keep]), np.ascontiguousarray(ids[keep])
+    n, dim = styles.shape
+    out.update(lines=n, dim=dim, writers=int(len(np.unique(ids))))
+    styles_d, ids_d = ops.h2d(styles, gpu), ops.h2d(ids, gpu)
+    fetches = [(name, ops.AsyncFetch(ops.writer_first_rank(styles_d, ids_d, metric)[0])) for name, metric in (("l1", ops.WID_L1), ("l2", ops.WID_L2))]
+    for name, fetch in fetches:
+        rank = fetch.get().numpy()
+        has = rank < n
+        part = {"top%d" % k: int((rank <= min(k, n - 1)).sum()) / n for k in tops}
+        part["mean_first_rank"] = int(rank[has].sum(dtype=np.int64)) / int(has.sum()) if has.any() else None
+        part["rows_without_match"] = int((~has).sum())
+        out[name] = part
+    return {k: out[k] for k in ("lines", "dim", "writers", "dropped", "l1", "l2") if k in out}

@@ -2535,6 +2535,39 @@ def ctc_error_rates(pred, gt, idx_to_char, casesensitive=True):
 
 
 # ----------------------------------------------------------------------------------------------
+# writer retrieval over style vectors: rank of the nearest other line of the same writer (csrc/writer_id.hip)
+# ----------------------------------------------------------------------------------------------
+WID_L1, WID_L2 = 0, 1                                   # hwg_writer_first_rank's metric: sum |a - b|, sum (a - b)^2
+
+
+def writer_first_rank(styles, author_ids, metric, out=None):
+    """styles [N, D] fp32 and author_ids [N] int32 on the device -> (first_rank int32 [N], nearest_same fp32 [N]): per row the place, in the
+    stable order of its distances to all rows, of the nearest entry of its writer that is not at place 0 (N where there is none) and the
+    distance there (+inf where there is none). `out`: a (first_rank, nearest_same) pair to write into."""
+    if not torch.is_tensor(styles) or styles.dim() != 2 or not styles.is_cuda or styles.dtype != torch.float32 or not styles.is_contiguous():
+        raise L.HwgError("writer_first_rank: styles must be a contiguous [N, D] fp32 device tensor, got %s %s" % (
+            tuple(styles.shape) if torch.is_tensor(styles) else type(styles), getattr(styles, "dtype", None)))
+    N, D = styles.shape
+    if not torch.is_tensor(author_ids) or tuple(author_ids.shape) != (N,) or author_ids.dtype != torch.int32 or \
+            author_ids.device != styles.device or not author_ids.is_contiguous():
+        raise L.HwgError("writer_first_rank: author_ids must be a contiguous [%d] int32 tensor on %s, got %s %s" % (
+            N, styles.device, tuple(author_ids.shape) if torch.is_tensor(author_ids) else type(author_ids), getattr(author_ids, "dtype", None)))
+    if metric not in (WID_L1, WID_L2):
+        raise L.HwgError("writer_first_rank: metric must be 0 (L1) or 1 (squared L2), got %r" % (metric,))
+    if out is None:
+        first_rank = torch.empty((N,), dtype=torch.int32, device=styles.device)
+        nearest_same = torch.empty((N,), dtype=torch.float32, device=styles.device)
+    else:
+        first_rank, nearest_same = out
+        if tuple(first_rank.shape) != (N,) or first_rank.dtype != torch.int32 or not first_rank.is_contiguous() or \
+                tuple(nearest_same.shape) != (N,) or nearest_same.dtype != torch.float32 or not nearest_same.is_contiguous() or \
+                first_rank.device != styles.device or nearest_same.device != styles.device:
+            raise L.HwgError("writer_first_rank: out must be contiguous (int32 [%d], fp32 [%d]) tensors on %s" % (N, N, styles.device))
+    L.call("hwg_writer_first_rank", styles, author_ids, N, D, int(metric), first_rank, nearest_same, _stream())
+    return first_rank, nearest_same
+
+
+# ----------------------------------------------------------------------------------------------
 # frozen BatchNorm (eval) and the FusedUpsample weight transform
 # ----------------------------------------------------------------------------------------------
 def norm_apply_frozen(x, running_mean, running_var, eps, gamma, beta, act=ACT_NONE, slope=0.0):

@@ -560,6 +560,20 @@ int hwg_lines_from_u8(const unsigned char* pixels, long long pixel_bytes, const 
 int hwg_ctc_error_rates(const float* pred, int T, int B, int C, const int* class_code, const int* ref_codes, const int* ref_offsets,
                         int max_ref_len, int* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Writer retrieval over style vectors (eval_writer_id.py:15-29 topN over the :70-81 all-pairs l1 / l2 / gt matrices - there nested
+ * Python loops, two N x N fp64 matrices and a Python sort per row).
+ * styles [N][D] fp32, author_id [N] int32 (equal ids = same writer); metric 0: sum |a - b|, 1: sum (a - b)^2 (no root), both one fp32
+ * chain over d ascending. Row i's columns are ordered by the key (distance, column) - a stable sort by distance -; pos_i(j) is column
+ * j's place in that order. first_rank [N] int32: min{pos_i(j) : author_id[j] == author_id[i], pos_i(j) >= 1} (j == i included: the row's
+ * own column counts unless it is at place 0), N where no such column exists; nearest_same [N] fp32: the distance at that place, +inf
+ * where there is none. Every entry of both is written. No N x N storage, no workspace: two launches (targets, counts), each computing
+ * all distances, bit-identically.
+ * Checked here before any launch: no NULL, N, D >= 1, metric 0 or 1, N <= 2^20, D <= 65536, styles 16-byte and the rest 4-byte aligned.
+ * ------------------------------------------------------------------------------------------ */
+int hwg_writer_first_rank(const float* styles, const int* author_id, int N, int D, int metric, int* first_rank, float* nearest_same,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

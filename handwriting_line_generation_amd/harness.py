@@ -18,6 +18,7 @@ CONFIGS = {
     "iam_gan": "cf_IAMslant_noMask_charSpecSingleAppend_GANMedMT_autoAEMoPrcp2tightNewCTCUseGen_balB_hCF0.75_sMG.json",
     "rimes_gan": "cf_RIMESLinesslant_noMask_charSpecSingleAppend_GANMedMT_autoAEMoPrcp2tightNewCTCUseGen_balB_hCF0.75_sMG.json",
     "iam_hwr": "cf_IAM_hwr_cnnOnly_batchnorm_aug.json",
+    "iam_hwr_crnn": "cf_IAM_hwr_crnn_batchnorm_aug.json",
     "iam_auto": "cf_IAM_auto_2tight_newCTC.json",
 }
 CHAR_FILES = {"iam": os.path.join(PKG, "data", "IAM_char_set.json"), "rimes": os.path.join(PKG, "data", "RIMES_characterset_lines.json")}
@@ -52,10 +53,13 @@ def synthetic_gan_config(which="iam_gan", batch_size=None, a_batch_size=None, wo
 
 
 def build_gan_trainer(which="iam_gan", batch_size=None, a_batch_size=None, width=512, label_len=30, min_width=None, workdir=None,
-                      gpu=0, rank=0, world=1, model_state=None, encoder_state=None, data_seed=100, resume=None, curriculum=None):
+                      gpu=0, rank=0, world=1, model_state=None, encoder_state=None, data_seed=100, resume=None, curriculum=None, hwr=None):
+    """hwr: replaces the config's `model.hwr` recogniser string (e.g. "CRNN batchnorm")"""
     if workdir is not None:
         os.makedirs(workdir, exist_ok=True)
     cfg, workdir = synthetic_gan_config(which, batch_size, a_batch_size, workdir, gpu)
+    if hwr is not None:
+        cfg["model"]["hwr"] = hwr
     tr = cfg["trainer"]
     if curriculum is not None:
         tr["curriculum"] = {"0": curriculum}
@@ -76,7 +80,8 @@ def build_gan_trainer(which="iam_gan", batch_size=None, a_batch_size=None, width
 
 
 def build_simple_trainer(which, batch_size=None, width=512, label_len=30, workdir=None, gpu=0, rank=0, world=1, model_state=None, data_seed=100):
-    """trainers of the two pre-training configs: 'iam_hwr' (CTC recogniser, BASELINE configs[0]) and 'iam_auto' (autoencoder, configs[1])"""
+    """trainers of the pre-training configs: 'iam_hwr' / 'iam_hwr_crnn' (CTC recogniser, BASELINE configs[0] and its CRNN twin) and 'iam_auto'
+    (autoencoder, configs[1])"""
     from .trainer import AutoTrainer
     cfg = copy.deepcopy(load_config(which))
     workdir = workdir or tempfile.mkdtemp(prefix="hwg_")

@@ -11,6 +11,60 @@ from .. import ops
 from .layers import BatchNorm1d, BatchNorm2d, Conv1d, Conv2d, GroupNorm, Marker, group_count
 
 
+def norm_kind_of(norm):
+    return "group" if (norm is not None and "group" in norm) else ("batch" if norm else None)
+
+
+def make_trunk(nc, norm_kind):
+    """the seven-conv trunk shared by the CNN-only recogniser and the CRNN (reference: cnn_only_hwr.py / cnn_lstm.py, the same Sequential)"""
+    CH, PADS, NORMED = CNNOnlyHWR.CHANNELS, CNNOnlyHWR.PADS, CNNOnlyHWR.NORMED
+    cnn = nn.Sequential()
+    for i, ch in enumerate(CH):
+        cin = nc if i == 0 else CH[i - 1]
+        cnn.add_module("conv%d" % i, Conv2d(cin, ch, 3, 1, PADS[i]))
+        if i in NORMED and norm_kind == "group":
+            cnn.add_module("groupnorm%d" % i, GroupNorm(group_count(ch), ch))
+        elif i in NORMED and norm_kind == "batch":
+            cnn.add_module("batchnorm%d" % i, BatchNorm2d(ch))
+        cnn.add_module("relu%d" % i, Marker("relu"))
+        if i in (0, 1):
+            cnn.add_module("pooling%d" % i, Marker("maxpool 2x2"))
+        elif i == 3:
+            cnn.add_module("pooling2", Marker("maxpool (2,2)/(2,1)/(0,1)"))
+        elif i == 5:
+            cnn.add_module("pooling3", Marker("maxpool (2,2)/(2,1)/(0,1)"))
+    return cnn
+
+
+def conv_block(cnn, norm_kind, i, x, pool=None):
+    """conv (+norm) + ReLU, followed by the max-pool `pool` = (kernel, stride, padding) of the reference's Sequential when there is one"""
+    conv = getattr(cnn, "conv%d" % i)
+    if i in CNNOnlyHWR.NORMED and norm_kind is not None:
+        h = conv(x)
+        norm = getattr(cnn, ("groupnorm%d" if norm_kind == "group" else "batchnorm%d") % i)
+        h = norm(h, "relu")
+        return ops.max_pool2d(h, *pool) if pool else h
+    # the bias is added in the conv epilogue (its gradient then rides along in the weight-gradient kernel); ReLU is one elementwise pass
+    h = ops.conv2d(x, conv.weight, conv.bias, conv.stride, conv.padding, conv.dilation)
+    if pool:
+        # ReLU after the pool instead of before it: max and ReLU are both monotone, relu(max(w)) == max(relu(w)) exactly, and the two
+        # orders route the gradient to the same window element wherever it is not zero anyway (a window whose maximum is <= 0 passes
+        # nothing back in either order) - same bits forward and backward, with the ReLU passes over a half / quarter of the pixels
+        return ops.max_pool2d(h, *pool, relu=True)          # (the ReLU rides along in the pooling kernels: hwg_maxpool_relu_*)
+    return ops.bias_act(h, None, None, ops.ACT_RELU)
+
+
+def run_trunk(cnn, norm_kind, x):
+    """NHWC [B,64,W,nc] -> [B,1,W/4-2,512]"""
+    x = conv_block(cnn, norm_kind, 0, x, (2, 2))
+    x = conv_block(cnn, norm_kind, 1, x, (2, 2))
+    x = conv_block(cnn, norm_kind, 2, x)
+    x = conv_block(cnn, norm_kind, 3, x, ((2, 2), (2, 1), (0, 1)))
+    x = conv_block(cnn, norm_kind, 4, x)
+    x = conv_block(cnn, norm_kind, 5, x, ((2, 2), (2, 1), (0, 1)))
+    return conv_block(cnn, norm_kind, 6, x)
+
+
 class CNNOnlyHWR(nn.Module):
     CHANNELS = [64, 128, 256, 256, 512, 512, 512]
     PADS = [1, 1, 1, 1, 1, 0, 0]
@@ -26,22 +80,8 @@ class CNNOnlyHWR(nn.Module):
             self.pad_cols = 128
         else:
             self.pad_cols = 0
-        self.norm_kind = "group" if (norm is not None and "group" in norm) else ("batch" if norm else None)
-        cnn = nn.Sequential()
-        for i, ch in enumerate(self.CHANNELS):
-            cin = nc if i == 0 else self.CHANNELS[i - 1]
-            cnn.add_module("conv%d" % i, Conv2d(cin, ch, 3, 1, self.PADS[i]))
-            if i in self.NORMED and self.norm_kind == "group":
-                cnn.add_module("groupnorm%d" % i, GroupNorm(group_count(ch), ch))
-            elif i in self.NORMED and self.norm_kind == "batch":
-                cnn.add_module("batchnorm%d" % i, BatchNorm2d(ch))
-            cnn.add_module("relu%d" % i, Marker("relu"))
-            if i in (0, 1):
-                cnn.add_module("pooling%d" % i, Marker("maxpool 2x2"))
-            elif i == 3:
-                cnn.add_module("pooling2", Marker("maxpool (2,2)/(2,1)/(0,1)"))
-            elif i == 5:
-                cnn.add_module("pooling3", Marker("maxpool (2,2)/(2,1)/(0,1)"))
+        self.norm_kind = norm_kind_of(norm)
+        cnn = make_trunk(nc, self.norm_kind)
         self.cnn = cnn
         size1d = 512
         mk = (lambda: GroupNorm(group_count(size1d), size1d)) if norm == "group" else (lambda: BatchNorm1d(size1d))
@@ -52,21 +92,7 @@ class CNNOnlyHWR(nn.Module):
         self.cnn1d = nn.Sequential(*layers)
 
     def _conv_block(self, i, x, pool=None):
-        """conv (+norm) + ReLU, followed by the max-pool `pool` = (kernel, stride, padding) of the reference's Sequential when there is one"""
-        conv = getattr(self.cnn, "conv%d" % i)
-        if i in self.NORMED and self.norm_kind is not None:
-            h = conv(x)
-            norm = getattr(self.cnn, ("groupnorm%d" if self.norm_kind == "group" else "batchnorm%d") % i)
-            h = norm(h, "relu")
-            return ops.max_pool2d(h, *pool) if pool else h
-        # the bias is added in the conv epilogue (its gradient then rides along in the weight-gradient kernel); ReLU is one elementwise pass
-        h = ops.conv2d(x, conv.weight, conv.bias, conv.stride, conv.padding, conv.dilation)
-        if pool:
-            # ReLU after the pool instead of before it: max and ReLU are both monotone, relu(max(w)) == max(relu(w)) exactly, and the two
-            # orders route the gradient to the same window element wherever it is not zero anyway (a window whose maximum is <= 0 passes
-            # nothing back in either order) - same bits forward and backward, with the ReLU passes over a half / quarter of the pixels
-            return ops.max_pool2d(h, *pool, relu=True)          # (the ReLU rides along in the pooling kernels: hwg_maxpool_relu_*)
-        return ops.bias_act(h, None, None, ops.ACT_RELU)
+        return conv_block(self.cnn, self.norm_kind, i, x, pool)
 
     logit_offset = None
 
@@ -86,13 +112,7 @@ class CNNOnlyHWR(nn.Module):
         x = ops.to_nhwc(input)
         if self.pad_cols:
             x = ops.pad2d(x, self.pad_cols, self.pad_cols, 0, 0, "constant", 0.0)
-        x = self._conv_block(0, x, (2, 2))
-        x = self._conv_block(1, x, (2, 2))
-        x = self._conv_block(2, x)
-        x = self._conv_block(3, x, ((2, 2), (2, 1), (0, 1)))
-        x = self._conv_block(4, x)
-        x = self._conv_block(5, x, ((2, 2), (2, 1), (0, 1)))
-        x = self._conv_block(6, x)
+        x = run_trunk(self.cnn, self.norm_kind, x)
         B, H, W, C = x.shape
         if H != 1:
             # the reference flattens (c,h) into channels; only height-1 features are meaningful for the shipped 64-px configs

@@ -15,6 +15,7 @@ from .. import ops, rng
 from ..logger import load_checkpoint
 from ..base.base_model import BaseModel
 from .char_style import CharStyleEncoder
+from .cnn_lstm import CRNN
 from .cnn_only_hwr import CNNOnlyHWR
 from .count_cnn import CountCNN
 from .discriminator_ap import DiscriminatorAP
@@ -78,10 +79,16 @@ class HWWithStyle(BaseModel):
             if pad and "pad less" in hwr_type:
                 pad = "less"
             self.hwr = CNNOnlyHWR(num_class, norm="group" if "group" in hwr_type else "batch", small="small" in hwr_type, pad=pad)
+        elif "CRNN" in hwr_type:
+            # the reference's parsing (hw_with_style.py:135-149): group / no_norm / batch; log-softmax always on; 'pad less' / 'pad'
+            if "small" in hwr_type or "sma32" in hwr_type:
+                raise NotImplementedError("recogniser %r: leakyRelu/small recogniser variants are not used by any shipped config" % hwr_type)
+            norm = "group" if "group" in hwr_type else (None if ("no_norm" in hwr_type or "no norm" in hwr_type) else "batch")
+            self.hwr = CRNN(num_class, norm=norm, use_softmax=True, pad="less" if "pad less" in hwr_type else "pad" in hwr_type)
         elif "none" in hwr_type:
             self.hwr = None
         else:
-            raise NotImplementedError("recogniser %r: only the CNN-only CTC recogniser is on the accelerated path" % hwr_type)
+            raise NotImplementedError("recogniser %r: only the CNN-only and CRNN CTC recognisers are on the accelerated path" % hwr_type)
         self.hwr_frozen = False
         pre = g("pretrained_hwr")
         if pre is not None:

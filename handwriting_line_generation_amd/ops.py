@@ -3038,3 +3038,179 @@ class _MLPChain(Function):
         else:
             L.call("hwg_mlp_chain_bwd", dout.contiguous(), acts, wptr, gw, gb, chain.L, B, D, chain.slope, dx, _stream())
         return (dx, None) + (None,) * (2 * chain.L)
+
+
+# ----------------------------------------------------------------------------------------------
+# bidirectional LSTM (csrc/lstm.hip): the CRNN recogniser's recurrence
+# ----------------------------------------------------------------------------------------------
+_lstm_pack_cache = {}     # (id(w_f), id(w_r)) -> [stamp, [2][H][4H] transposed image, (w_f, w_r)]
+
+
+def _weight_stamp(w):
+    return (w.data_ptr(), w._version, WEIGHT_EPOCH.get(getattr(w, "_hwg_group", None), 0))
+
+
+def _lstm_packed_whh(w_f, w_r):
+    """the [2][H][4H] image of W_hh the backward kernel reads: written once per weight epoch for parameters (as _pack does for conv weights),
+    per call for anything else"""
+    H = w_f.shape[1]
+    cacheable = isinstance(w_f, torch.nn.Parameter) and isinstance(w_r, torch.nn.Parameter)
+    key = stamp = hit = None
+    if cacheable:
+        key, stamp = (id(w_f), id(w_r)), (_weight_stamp(w_f), _weight_stamp(w_r))
+        hit = _lstm_pack_cache.get(key)
+        if hit is not None and hit[0] == stamp:
+            return hit[1]
+    out = hit[1] if hit is not None else torch.empty((2, H, 4 * H), dtype=torch.float32, device=w_f.device)
+    L.call("hwg_lstm_pack_whh", w_f, w_r, H, out, _stream())
+    if cacheable:
+        _lstm_pack_cache[key] = [stamp, out, (w_f, w_r)]
+    return out
+
+
+def _linear_wgrad(x2d, dy2d, weight):
+    """dW [O, I] = dy2d^T x2d through the convolution weight-gradient path (one GEMM over all rows). -> the gradient as a tensor, or None where the
+    kernel accumulated straight into the parameter's gradient buffer"""
+    rows, I = x2d.shape
+    ctx = _TapeCtx((False, True, False))
+    ctx.saved_tensors = (x2d.view(rows, 1, 1, I), weight)
+    ctx.scope = SCOPE
+    ctx.has_bias = False
+    ctx.param_refs = (weight, None)
+    ctx.geom = ((1, 1), (0, 0), (1, 1), False, 1, 1)
+    return _Conv2d._wgrad(ctx, dy2d.view(rows, 1, 1, dy2d.shape[1]))[0]
+
+
+class _LSTMLayer(Function):
+    """one bidirectional LSTM layer given its input projections: xp_f / xp_r [T,B,4H] (x W_ih^T + b_ih of the forward / reverse direction),
+    W_hh [4H,H] and b_hh [4H] per direction -> y [T,B,2H]"""
+
+    @staticmethod
+    def forward(ctx, xp_f, xp_r, w_f, w_r, b_f, b_r, may_keep):
+        for t_, n_ in ((xp_f, "lstm xproj"), (xp_r, "lstm xproj (reverse)"), (w_f, "lstm W_hh"), (w_r, "lstm W_hh (reverse)"), (b_f, "lstm b_hh"), (b_r, "lstm b_hh (reverse)")):
+            _chk(t_, n_)
+        T, B, G = xp_f.shape
+        H = G // 4
+        if tuple(w_f.shape) != (G, H) or tuple(w_r.shape) != (G, H) or b_f.numel() != G or b_r.numel() != G or tuple(xp_r.shape) != (T, B, G) or G != 4 * H:
+            raise L.HwgError("lstm_layer: shapes do not fit (xproj %s / %s, W_hh %s / %s)" % (tuple(xp_f.shape), tuple(xp_r.shape), tuple(w_f.shape), tuple(w_r.shape)))
+        dev = xp_f.device
+        y = torch.empty((T, B, 2 * H), dtype=torch.float32, device=dev)
+        # what the backward pass reads (gates, c, the h_prev rows) is written only when one can follow. `may_keep` is lstm_layer's answer to
+        # "is a tape recording, or is autograd" - asked THERE, because inside a Function's forward grad mode is always off, and torch fills
+        # needs_input_grad from requires_grad whatever the mode outside. Train and eval mode alike: the GAN lessons differentiate through a
+        # recogniser either way. Otherwise - validation, any forward under no_grad - two ping-pong c buffers.
+        keep = bool(may_keep) and any(ctx.needs_input_grad[:6])
+        if keep:
+            gates = torch.empty((2, T, B, G), dtype=torch.float32, device=dev)
+            c = torch.empty((2, T, B, H), dtype=torch.float32, device=dev)
+            hseq = torch.empty((2, T + 1, B, H), dtype=torch.float32, device=dev)
+        else:
+            gates = hseq = None
+            c = workspace(2 * 2 * B * H * 4, dev)
+        L.call("hwg_lstm_fwd", xp_f, xp_r, w_f, w_r, b_f, b_r, y, gates, c, hseq, T, B, H, int(keep), _stream())
+        if keep:
+            ctx.save_for_backward(gates, c, hseq, w_f, w_r)
+            ctx.param_refs = (w_f, w_r, b_f, b_r)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        gates, c, hseq, w_f, w_r = ctx.saved_tensors
+        _, T, B, G = gates.shape
+        H = G // 4
+        dev = gates.device
+        wt = _lstm_packed_whh(w_f, w_r)
+        dgates = torch.empty_like(gates)
+        ws = workspace(2 * 2 * B * H * 4, dev)
+        L.call("hwg_lstm_bwd", dy.contiguous(), gates, c, wt, dgates, ws, T, B, H, _stream())
+        need = ctx.needs_input_grad
+        wf_ref, wr_ref, bf_ref, br_ref = ctx.param_refs
+        out = [dgates[0] if need[0] else None, dgates[1] if need[1] else None, None, None, None, None, None]
+        for d, (wref, bref) in enumerate(((wf_ref, bf_ref), (wr_ref, br_ref))):
+            dg2 = dgates[d].view(T * B, G)
+            if need[2 + d]:
+                hprev = (hseq[0, :T] if d == 0 else hseq[1, 1:]).reshape(T * B, H)      # (contiguous row ranges: views)
+                out[2 + d] = _linear_wgrad(hprev, dg2, wref)
+            if need[4 + d]:
+                if _direct(bref):
+                    colsum(dg2, out=_grad_buffer(bref).view(-1), accumulate=True)
+                else:
+                    out[4 + d] = colsum(dg2).view(bref.shape)
+        return tuple(out)
+
+
+def _pair_of(v, what):
+    if isinstance(v, torch.Tensor):
+        if v.shape[0] != 2:
+            raise L.HwgError("lstm_layer: %s must be a (forward, reverse) pair or a tensor stacked [2, ...]" % what)
+        return v[0], v[1]
+    a, b = v
+    return a, b
+
+
+def lstm_layer(xproj, w_hh, b_hh, training=False):
+    """One bidirectional LSTM layer. Each of xproj, w_hh, b_hh is a (forward, reverse) pair - or one tensor stacked [2, ...] -: xproj [T,B,4H]
+    per direction (the input projection x W_ih^T + b_ih, an ops.linear per direction, which owns dx and dW_ih), w_hh [4H,H], b_hh [4H].
+    -> y [T,B,2H], forward direction in [..., :H]. The gates are kept for a backward pass exactly when one can follow (autograd is recording
+    and an input requires grad, or a tape records the call); under no_grad the kernel keeps two ping-pong c buffers instead. `training` is not
+    read: the layer computes the same thing in train and eval mode (the dropout between layers is ops.bilstm's business); the argument is
+    kept only so that the call reads like its siblings."""
+    xf, xr = _pair_of(xproj, "xproj")
+    wf, wr = _pair_of(w_hh, "w_hh")
+    bf, br = _pair_of(b_hh, "b_hh")
+    # (the rule of adain_epilogue: a tape, or autograd recording with something to differentiate)
+    may_keep = TAPE is not None or (torch.is_grad_enabled() and any(t.requires_grad for t in (xf, xr, wf, wr, bf, br)))
+    return _LSTMLayer.apply(xf, xr, wf, wr, bf, br, may_keep)
+
+
+def lstm_limits(H):
+    """(unit slice, batch tile) of the LSTM kernels for hidden size H: H must be a multiple of the slice; wider batches run in tiles"""
+    return int(L.query("hwg_lstm_unit_slice")), int(L.query("hwg_lstm_batch_tile", int(H)))
+
+
+def bilstm(x_TBC, params, p_drop, training, masks=None):
+    """Stacked bidirectional LSTM. x [T,B,I]; params: per layer ((w_ih_f, w_hh_f, b_ih_f, b_hh_f), (the same four of the reverse direction)).
+    Per layer: ops.linear per direction -> lstm_layer -> (between layers, training with p_drop > 0 only) an elementwise dropout multiplier
+    over [T,B,2H] holding 0 or 1/(1-p): rng.seq_mask, or `masks[layer]` when supplied. -> [T,B,2H]"""
+    from . import rng
+    T, B, _ = x_TBC.shape
+    h = x_TBC
+    for li, (pf, pr) in enumerate(params):
+        rows = h.contiguous().view(T * B, h.shape[2])
+        G = pf[0].shape[0]
+        xf = linear(rows, pf[0], pf[2]).view(T, B, G)
+        xr = linear(rows, pr[0], pr[2]).view(T, B, G)
+        h = lstm_layer((xf, xr), (pf[1], pr[1]), (pf[3], pr[3]), training)
+        if li + 1 < len(params):
+            m = masks[li] if masks is not None else (rng.seq_mask(tuple(h.shape), p_drop, h.device) if (training and p_drop > 0) else None)
+            if m is not None:
+                h = mul_const(h, m)
+    return h
+
+
+# ----------------------------------------------------------------------------------------------
+# cache maintenance
+# ----------------------------------------------------------------------------------------------
+def _cache_dicts():
+    from . import replay
+    return [_pack_cache, _pack_tables, _lstm_pack_cache, _set_views, replay._programs]
+
+
+def cache_mark():
+    """what the module-level caches hold now (packed weight images and their refresh tables, the LSTM's transposed W_hh images, gradient-set
+    views, recorded replay programs): hand it to drop_caches(since=...) later to drop only what was added in between"""
+    return [set(c.keys()) for c in _cache_dicts()]
+
+
+def drop_caches(since=None):
+    """Forget cached images / programs: all of them, or those added after `since` (a cache_mark()). The caches reference every parameter they
+    have seen for the rest of the process - and through a parameter's flat-buffer attributes its trainer -; a process that builds models or
+    trainers it is done with (tests, sweeps) calls this to let them go. Everything dropped is rebuilt on next use. -> entries dropped"""
+    n = 0
+    dicts = _cache_dicts()
+    for c, keep in zip(dicts, since if since is not None else [()] * len(dicts)):
+        for k in [k for k in c if k not in keep]:
+            del c[k]
+            n += 1
+    return n
+

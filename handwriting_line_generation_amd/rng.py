@@ -155,3 +155,11 @@ def element_mask(x, p):
         m = torch.empty(N, C, H, W).bernoulli_(1 - p).div_(1 - p)
         return m.permute(0, 2, 3, 1).contiguous().to(x.device)
     return _dev_rng().dropmask((N, H, W, C), p, x.device)
+
+
+def seq_mask(shape, p, device):
+    """elementwise dropout multiplier over a [T,B,C] sequence tensor (the dropout between the layers of a stacked LSTM): 0 or 1/(1-p)"""
+    T, B, C = shape
+    if _state["mode"] == "host":
+        return torch.empty(T, B, C).bernoulli_(1 - p).div_(1 - p).to(device)
+    return _dev_rng().dropmask((T, B, C), p, device)

@@ -574,6 +574,30 @@ int hwg_ctc_error_rates(const float* pred, int T, int B, int C, const int* class
 int hwg_writer_first_rank(const float* styles, const int* author_id, int N, int D, int metric, int* first_rank, float* nearest_same,
                           void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * One bidirectional LSTM layer (csrc/lstm.hip; torch.nn.LSTM gate order i, f, g, o and arithmetic, accurate expf / tanhf).
+ * The input projection x W_ih^T + b_ih is NOT part of these calls (it is a linear layer, run and differentiated as one): xproj_f / xproj_r
+ * are its two halves, [T][B][4H] each, for the forward and the reverse direction. whh_* [4H][H], bhh_* [4H].
+ * y [T][B][2H]: forward direction in [..., :H], reverse in [..., H:]; step t reads h_{t-1} out of y's neighbouring time row.
+ * training != 0: also writes gates [2][T][B][4H] (post-activation), c [2][T][B][H] and hseq [2][T+1][B][H] (direction 0: row t + 1 = h_t, row 0
+ * zero; direction 1: row t = h_t, row T zero - so that rows 0..T-1 of direction 0 and rows 1..T of direction 1 are the h_prev matrices of the
+ * W_hh gradient's GEMM). training == 0: gates / hseq may be NULL and c is a [2][2][B][H] ping-pong workspace.
+ * One launch per time step, both directions in it; no allocation, no host synchronisation, nothing waits on another workgroup inside a
+ * launch. Summation order of the recurrent dot product: fixed, documented at the top of csrc/lstm.hip (depends on H alone).
+ * hwg_lstm_bwd walks t the other way: launch t forms dh_rec = dgates[t+-1] W_hh for its units from whh_t, the [2][H][4H] transposed image
+ * written by hwg_lstm_pack_whh (once per weight epoch), then the gate backward, and writes dgates [2][T][B][4H] (= d xproj; its column sums
+ * are d b_hh, dgates[d]^T hseq-rows[d] is d W_hh[d] - both through the existing kernels). dc_ws: [2][2][B][H] ping-pong workspace.
+ * Limits, checked before any launch: T, B >= 1, H a multiple of hwg_lstm_unit_slice() and <= 1024, T*B*4H < 2^31; W_hh, y, dgates and whh_t
+ * 16-byte aligned. A batch wider than hwg_lstm_batch_tile(H) lines (the LDS image, min(32, 16384 / H)) is walked in tiles of that many.
+ * ------------------------------------------------------------------------------------------ */
+int hwg_lstm_unit_slice(void);
+int hwg_lstm_batch_tile(int H);
+int hwg_lstm_fwd(const float* xproj_f, const float* xproj_r, const float* whh_f, const float* whh_r, const float* bhh_f, const float* bhh_r,
+                 float* y, float* gates, float* c, float* hseq, int T, int B, int H, int training, void* stream);
+int hwg_lstm_bwd(const float* dy, const float* gates, const float* c, const float* whh_t, float* dgates, float* dc_ws, int T, int B, int H,
+                 void* stream);
+int hwg_lstm_pack_whh(const float* whh_f, const float* whh_r, int H, float* whh_t, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2441,6 +2441,69 @@ def lines_from_u8(pixels, offsets, widths, select, real=None, out=None, height=6
 
 
 # ----------------------------------------------------------------------------------------------
+# sample sheets of GAN training: a batch of lines as one 8-bit grey picture (csrc/sample_sheet.hip)
+# ----------------------------------------------------------------------------------------------
+def sample_sheet_shape(B, H, W, nrow=None):
+    """(rows, columns, nrow) of the sheet torchvision's make_grid lays out for B images of H x W with padding 2; nrow=None: the
+    reference's max(1, 2048 // W)"""
+    nrow = max(1, 2048 // W) if nrow is None else int(nrow)
+    if nrow < 1:
+        raise L.HwgError("sample_sheet: nrow %d, need at least 1" % nrow)
+    if B == 1:
+        return H, W, nrow
+    xmaps = min(nrow, B)
+    ymaps = -(-B // xmaps)
+    return (H + 2) * ymaps + 2, (W + 2) * xmaps + 2, nrow
+
+
+def sample_sheet(images, nrow=None, out=None):
+    """`images` [B,1,H,W] (device, fp32) -> the uint8 device tensor [Hs, Ws] that the reference's save_image(1 - images, nrow=nrow,
+    normalize=True) writes to disk: normalised to the batch's own range, tiled nrow to a row with a border of 2, quantised with + 0.5
+    (hwg_sheet_minmax + hwg_sheet_compose: two launches on the current stream, nothing comes to the host). nrow=None: max(1, 2048 // W).
+    `out`: a contiguous 4-byte aligned uint8 device buffer of at least Hs * Ws bytes rounded up to 4 to write into (every byte of the sheet
+    is written; the returned tensor is a view of it)."""
+    if not torch.is_tensor(images) or images.dim() != 4 or images.shape[1] != 1 or min(images.shape) < 1:
+        raise L.HwgError("sample_sheet: images must be a [B,1,H,W] fp32 device tensor, got %s" % (tuple(images.shape) if torch.is_tensor(images) else type(images),))
+    _chk(images, "sample_sheet: images")
+    B, _, H, W = images.shape
+    Hs, Ws, nrow = sample_sheet_shape(B, H, W, nrow)
+    if Hs * Ws > (1 << 31) - 4:
+        raise L.HwgError("sample_sheet: a sheet of %d x %d bytes does not fit int" % (Hs, Ws))
+    need = -(-Hs * Ws // 4) * 4
+    if out is None:
+        out = torch.empty((need,), dtype=torch.uint8, device=images.device)
+    else:
+        _chk(out, "sample_sheet: out", torch.uint8)
+        if out.numel() < need or out.data_ptr() % 4:
+            raise L.HwgError("sample_sheet: out must be a 4-byte aligned uint8 device buffer of at least %d bytes (the %d x %d sheet rounded up "
+                             "to 4), got %d" % (need, Hs, Ws, out.numel()))
+    n = B * H * W
+    parts = L.query("hwg_sheet_parts", n)
+    partials = torch.empty((parts, 2), dtype=torch.float32, device=images.device)
+    st = _stream()
+    L.call("hwg_sheet_minmax", images, n, partials, parts, st)
+    L.call("hwg_sheet_compose", images, B, H, W, nrow, partials, parts, out, out.numel(), st)
+    return out.view(-1)[:Hs * Ws].view(Hs, Ws)
+
+
+def row_means(rows2d, n_rows=None, out=None):
+    """fp32 mean of each of the first n_rows rows of a contiguous device [N, n] tensor -> [n_rows] (hwg_sheet_row_means, one launch);
+    `out`: a contiguous fp32 device tensor of at least n_rows elements to write into"""
+    _chk(rows2d, "row_means: input")
+    if rows2d.dim() != 2 or rows2d.shape[0] < 1 or rows2d.shape[1] < 1:
+        raise L.HwgError("row_means: input must be [N, n], got %s" % (tuple(rows2d.shape),))
+    n_rows = rows2d.shape[0] if n_rows is None else min(int(n_rows), rows2d.shape[0])
+    if out is None:
+        out = torch.empty((n_rows,), dtype=torch.float32, device=rows2d.device)
+    else:
+        _chk(out, "row_means: out")
+        if out.numel() < n_rows:
+            raise L.HwgError("row_means: out holds %d elements, %d rows asked for" % (out.numel(), n_rows))
+    L.call("hwg_sheet_row_means", rows2d, rows2d.shape[1], n_rows, rows2d.shape[1], out, _stream())
+    return out
+
+
+# ----------------------------------------------------------------------------------------------
 # recognition error rates: arg-max, greedy CTC decode, CER / WER counts on the device (csrc/error_rate.hip)
 # ----------------------------------------------------------------------------------------------
 ER_MAX_T, ER_MAX_C, ER_MAX_REF = 8192, 1024, 2047       # the limits hwg_ctc_error_rates checks

@@ -105,9 +105,13 @@ class HWWithStyleTrainer(BaseTrainer):
             self.encoder.load_state_dict(enc_sd)
             self.encoder = self.encoder.to(self.gpu)   # stays in train mode: its Dropout2d is live in the perceptual loss
 
-        self.print_dir = None  # sample image dumps need torchvision; not part of the accelerated path
         self.casesensitive = tr.get("casesensitive", True)
         self.world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+        # sample sheets (trainer :164-172): generated lines, reconstructions next to their ground truth and the discriminator's scores,
+        # composed on the device and written by a thread of their own (sample_sheets.py); None = no print_dir, the schedule is not run
+        self.print_dir = self._sheets = None
+        if tr.get("print_dir") is not None:
+            self.enable_sample_sheets(tr["print_dir"], tr.get("print_every", 100), tr.get("serperate_print_every", 2500))
         # control-plane group for host-side decisions every rank must take together (skip an iteration): CPU tensors over gloo, so
         # the exchange never waits for the GPU stream the way a device collective + .item() would
         self._dp = self.world > 1 or (flat_params_mod.FORCE_DP and dist.is_available() and dist.is_initialized())
@@ -151,6 +155,32 @@ class HWWithStyleTrainer(BaseTrainer):
         self._grad_switch = None
 
     # ------------------------------------------------------------------------------------------
+    def enable_sample_sheets(self, directory, print_every=100, serperate_print_every=2500):
+        """every `print_every` GAN iterations (the reference's schedule, sample_sheets.PrintSchedule) write into `directory`:
+        gen_samples_<n>.png + gen_text_<n>.txt at a lesson with "gen", then recon_samples_<n>.png + recon_gt_<n>.png at the next lesson with
+        "auto" (and the other way round), <n> = latest, or the iteration once per `serperate_print_every` iterations. The printing
+        iteration is an ordinary training iteration; data parallel: only rank 0 fetches and writes."""
+        from .sample_sheets import SheetPrinter
+        self.finish_sample_sheets()
+        self.print_dir = directory
+        self._sheets = SheetPrinter(directory, print_every, serperate_print_every, write=self.rank == 0, logger=self.logger)
+        return self._sheets
+
+    def finish_sample_sheets(self):
+        """wait for the print in flight: afterwards every announced file exists and the writer thread has ended"""
+        if getattr(self, "_sheets", None) is not None:
+            self._sheets.wait()
+
+    def train(self):
+        try:
+            return super().train()
+        finally:
+            self.finish_sample_sheets()
+
+    def _save_checkpoint(self, iteration, log, save_best=False, minor=False):
+        self.finish_sample_sheets()
+        return super()._save_checkpoint(iteration, log, save_best=save_best, minor=minor)
+
     def _to_tensor(self, instance):
         image, label = instance["image"], instance["label"]
         if image is not None:
@@ -206,6 +236,7 @@ class HWWithStyleTrainer(BaseTrainer):
         if self._side_wgrad == "auto":
             ops.SIDE_WGRAD = bool(lesson) and "auto" in lesson
         instance = self._next_instance(lesson or [])
+        self._sheet_iteration = iteration
         produced = self._forward_backward(instance, lesson)
         if produced is None:
             return {}
@@ -247,8 +278,10 @@ class HWWithStyleTrainer(BaseTrainer):
             if taped:
                 gen.tape_mode = True
                 self.model.style_tape_mode = self._tape_style
+            # (behind the skip, as in the reference: only iterations that train reach the print schedule, trainer :245-267)
+            sheet = self._sheets.schedule.step(lesson) if self._sheets is not None else None
             try:
-                losses = self.run_gen(instance, lesson)
+                losses = self.run_gen(instance, lesson, sheet=sheet)
             finally:
                 if taped:
                     gen.tape_mode = False
@@ -490,9 +523,12 @@ class HWWithStyleTrainer(BaseTrainer):
         recog = self.loss["recog"](pred, label.permute(1, 0), [T] * B, instance["label_lengths"])
         return pred, {"recogLoss": recog}
 
-    def run_gen(self, instance, lesson, get=[]):
+    def run_gen(self, instance, lesson, get=[], sheet=None):
+        """sheet: "gen" / "recon" = this iteration prints a sample sheet (trainer :248-264, there get=['gen', 'disc'] / ['recon'] and a
+        download): the same launches and draws as without, plus SheetPrinter.enqueue on what the lesson produced anyway"""
         model = self.model
         image, label = self._to_tensor(instance)
+        real_image = image                   # (as collated: `image` below is padded to the generated widths)
         batch_size = label.size(1)
         label_lengths = instance["label_lengths"]
         a_batch_size = self.a_batch_size if "a_batch_size" in instance else None
@@ -627,7 +663,14 @@ class HWWithStyleTrainer(BaseTrainer):
                 gen_loss = term if isinstance(gen_loss, int) else ops.add(gen_loss, term)
                 if "disc" in get:
                     predicted_disc.append(gp.detach().mean(dim=1).cpu())
+                elif sheet == "gen":
+                    predicted_disc.append(gp)
             losses["generatorLoss"] = ops.scale(gen_loss, 1.0 / len(gen_pred))
+
+        if sheet == "gen":
+            self._sheets.enqueue("gen", getattr(self, "_sheet_iteration", 0), gen_image, instance["gt"], disc=predicted_disc)
+        elif sheet == "recon":
+            self._sheets.enqueue("recon", getattr(self, "_sheet_iteration", 0), recon, instance["gt"], gt_images=real_image)
 
         ret = losses
         if get:

@@ -544,6 +544,29 @@ int hwg_lines_from_u8(const unsigned char* pixels, long long pixel_bytes, const 
                       const int* select, int min_select, const float* real, int Br, int Wr, int B, int H, int W, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Sample sheets of GAN training (trainer/hw_with_style_trainer.py:992-1010: torchvision's save_image(1 - images, nrow, normalize=True),
+ * there on the host after downloading the fp32 batch). x: images [B][1][H][W] fp32, n = B * H * W.
+ * v = 1 - x; lo / hi = min / max of the finite v over the whole tensor; d = (float)max((double)hi - (double)lo, 1e-5);
+ * level = trunc(clamp(((clamp(v, lo, hi) - lo) / d) * 255 + 0.5, 0, 255)), every operation rounded to fp32 on its own (no fma).
+ * A NaN pixel is 0; v = +inf is 255, v = -inf is 0; without any finite value the whole sheet is 0.
+ * B == 1: the sheet is the H x W image. Otherwise xmaps = min(nrow, B), ymaps = ceil(B / xmaps): (H + 2) ymaps + 2 rows of
+ * (W + 2) xmaps + 2 bytes, image k at row (k / xmaps)(H + 2) + 2 and column (k % xmaps)(W + 2) + 2, everything else 0.
+ * hwg_sheet_minmax: partials [n_parts][2] fp32 = (min, max) per workgroup, n_parts = hwg_sheet_parts(n) (at most 256); no atomics.
+ * hwg_sheet_compose: folds the partials in every workgroup, then writes EVERY byte of the sheet, one aligned 32-bit store per lane
+ * (a lane owns 4 consecutive bytes of the flat sheet; W is arbitrary). out_bytes: the bytes out holds, at least the sheet rounded up to
+ * 4 bytes; the bytes between the sheet's end and that bound are written 0, none beyond it is touched.
+ * Checked here before the launch: no NULL, B, H, W > 0, nrow >= 1, n_parts, sheet rows, columns and bytes fit int, out_bytes, x / partials
+ * / out 4-byte aligned.
+ * hwg_sheet_row_means: out[r] = fp32 mean of src[r * stride .. r * stride + n) for r < rows (the per-line discriminator means of
+ * gen_text_*.txt, :1016-1021), one workgroup per row.
+ * ------------------------------------------------------------------------------------------ */
+int hwg_sheet_parts(long long n);
+int hwg_sheet_minmax(const float* x, long long n, float* partials, int n_parts, void* stream);
+int hwg_sheet_compose(const float* x, int B, int H, int W, int nrow, const float* partials, int n_parts, unsigned char* out,
+                      long long out_bytes, void* stream);
+int hwg_sheet_row_means(const float* src, long long stride, int rows, int n, float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Recognition error rates on the device (trainer/hw_with_style_trainer.py:894-914 getCER, utils/string_utils.py naive_decode,
  * utils/error_rates.py:2-26 cer / wer - there on the host, after downloading the whole prediction).
  * pred [T][B][C] fp32 (the recogniser's output as it stands); class_code [C] int32: the code point class c compares as (32 for every

@@ -2504,6 +2504,68 @@ def row_means(rows2d, n_rows=None, out=None):
 
 
 # ----------------------------------------------------------------------------------------------
+# evaluation pictures of new_eval.py: the real line above its reconstruction, framed, captioned (csrc/eval_pictures.hip)
+# ----------------------------------------------------------------------------------------------
+def eval_pairs_shape(H, Wi, Wr, strip):
+    """(rows, columns) of one picture of eval_pairs: 2 H + 2 rows (+ the 50 rows of the caption strip), max(Wi, Wr) columns"""
+    return 2 * int(H) + 2 + (L.query("hwg_eval_strip_rows") if strip else 0), max(int(Wi), int(Wr))
+
+
+def eval_pairs(image, recon, captions=None, atlas=None, out=None):
+    """`image` [B,1,H,Wi] and `recon` [B,1,H,Wr] (device, fp32) -> the uint8 device tensor [B, Hp, Wp, 3] of the reference's per-line
+    evaluation pictures, RGB: the real line in a green frame above the reconstruction in a blue one, the narrower of the two centred.
+    `captions`: per line a sequence of glyph codes (a host list / array, -1 ends a caption; rows may differ in length) drawn from `atlas`
+    (uint8 device tensor [G, gh, gw]) into a strip of 50 rows below; None: no strip. Codes are checked on the host, before the one small
+    upload and the one launch (hwg_eval_pairs) on the current stream. `out`: a contiguous 4-byte aligned uint8 device buffer of at least
+    B * Hp * Wp * 3 bytes rounded up to 4 to write into (every byte is written; the returned tensor is a view of it)."""
+    import numpy as np
+    for t, name in ((image, "image"), (recon, "recon")):
+        if not torch.is_tensor(t) or t.dim() != 4 or t.shape[1] != 1 or min(t.shape) < 1:
+            raise L.HwgError("eval_pairs: %s must be a [B,1,H,W] fp32 device tensor, got %s" % (name, tuple(t.shape) if torch.is_tensor(t) else type(t)))
+        _chk(t, "eval_pairs: " + name)
+    B, _, H, Wi = image.shape
+    if recon.shape[0] != B or recon.shape[2] != H:
+        raise L.HwgError("eval_pairs: image %s and recon %s differ in lines or height" % (tuple(image.shape), tuple(recon.shape)))
+    Wr = recon.shape[3]
+    strip = captions is not None
+    Hp, Wp = eval_pairs_shape(H, Wi, Wr, strip)
+    total = B * Hp * Wp * 3
+    if total > (1 << 31) - 4:
+        raise L.HwgError("eval_pairs: %d pictures of %d x %d x 3 bytes do not fit int" % (B, Hp, Wp))
+    need = -(-total // 4) * 4
+    codes_d, G, gh, gw, n_codes = None, 0, 0, 0, 0
+    if strip:
+        if not torch.is_tensor(atlas) or atlas.dim() != 3 or min(atlas.shape) < 1:
+            raise L.HwgError("eval_pairs: captions need a glyph atlas, a uint8 device tensor [G, gh, gw]")
+        _chk(atlas, "eval_pairs: atlas", torch.uint8)
+        G, gh, gw = atlas.shape
+        if gh > Hp - 2 * H - 2:
+            raise L.HwgError("eval_pairs: glyphs of %d rows do not fit the strip of %d" % (gh, Hp - 2 * H - 2))
+        if len(captions) != B:
+            raise L.HwgError("eval_pairs: %d captions for %d lines" % (len(captions), B))
+        n_codes = max(1, min(max(len(c) for c in captions), -(-Wp // gw)))        # cells beyond the picture are never drawn: not uploaded
+        codes = np.full((B, n_codes), -1, dtype=np.int32)
+        for b, c in enumerate(captions):
+            c = np.asarray(c, dtype=np.int64).reshape(-1)
+            end = np.flatnonzero(c < 0)
+            c = c[:end[0]] if end.size else c                                      # -1 ends a caption: what follows it is not drawn
+            if c.size and c.max() >= G:
+                raise L.HwgError("eval_pairs: caption %d holds code %d, the atlas has %d glyphs" % (b, int(c.max()), G))
+            c = c[:n_codes]
+            codes[b, :c.size] = c
+        codes_d = h2d(codes, image.device)
+    if out is None:
+        out = torch.empty((need,), dtype=torch.uint8, device=image.device)
+    else:
+        _chk(out, "eval_pairs: out", torch.uint8)
+        if out.numel() < need or out.data_ptr() % 4:
+            raise L.HwgError("eval_pairs: out must be a 4-byte aligned uint8 device buffer of at least %d bytes (%d pictures of %d x %d x 3 rounded "
+                             "up to 4), got %d" % (need, B, Hp, Wp, out.numel()))
+    L.call("hwg_eval_pairs", image, recon, B, H, Wi, Wr, atlas if strip else None, G, gh, gw, codes_d, n_codes, out, out.numel(), _stream())
+    return out.view(-1)[:total].view(B, Hp, Wp, 3)
+
+
+# ----------------------------------------------------------------------------------------------
 # recognition error rates: arg-max, greedy CTC decode, CER / WER counts on the device (csrc/error_rate.hip)
 # ----------------------------------------------------------------------------------------------
 ER_MAX_T, ER_MAX_C, ER_MAX_REF = 8192, 1024, 2047       # the limits hwg_ctc_error_rates checks

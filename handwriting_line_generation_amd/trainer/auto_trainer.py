@@ -74,7 +74,8 @@ class AutoTrainer(BaseTrainer):
         log = dict(zip(names, host))
         return {"loss": sum(log.values()), **log}
 
-    def run_gen(self, instance, get=[]):
+    def run_gen(self, instance, get=[], on_device=False):
+        """on_device: accepted for symmetry with HWWithStyleTrainer.run_gen - the tensors of `got` are never downloaded here"""
         image = ops.h2d(instance["image"], self.gpu)
         label = ops.h2d(instance["label"], self.gpu)
         if image.size(3) % 8 > 0:

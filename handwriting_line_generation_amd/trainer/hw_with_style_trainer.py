@@ -523,9 +523,11 @@ class HWWithStyleTrainer(BaseTrainer):
         recog = self.loss["recog"](pred, label.permute(1, 0), [T] * B, instance["label_lengths"])
         return pred, {"recogLoss": recog}
 
-    def run_gen(self, instance, lesson, get=[], sheet=None):
+    def run_gen(self, instance, lesson, get=[], sheet=None, on_device=False):
         """sheet: "gen" / "recon" = this iteration prints a sample sheet (trainer :248-264, there get=['gen', 'disc'] / ['recon'] and a
-        download): the same launches and draws as without, plus SheetPrinter.enqueue on what the lesson produced anyway"""
+        download): the same launches and draws as without, plus SheetPrinter.enqueue on what the lesson produced anyway.
+        on_device: the tensors of `got` stay on the device (detached) instead of being downloaded: the evaluator composes its pictures and
+        counts its error rates there."""
         model = self.model
         image, label = self._to_tensor(instance)
         real_image = image                   # (as collated: `image` below is padded to the generated widths)
@@ -675,21 +677,30 @@ class HWWithStyleTrainer(BaseTrainer):
         ret = losses
         if get:
             got = {}
+            keep = (lambda t: t.detach()) if on_device else (lambda t: t.detach().cpu())
             for name in get:
                 if name == "recon":
-                    got[name] = recon.detach().cpu()
+                    got[name] = keep(recon)
                 elif name in ("gen", "gen_image", "gen_img"):
-                    got[name] = gen_image.detach().cpu()
+                    got[name] = keep(gen_image)
                 elif name == "pred":
                     if model.pred is None:
                         model.pred = model.hwr(image, None)
-                    got[name] = model.pred.detach().cpu()
+                    got[name] = keep(model.pred)
                 elif name == "style":
-                    got[name] = style.detach().cpu()
+                    got[name] = keep(style)
+                elif name == "spaced_label":         # the DTW index [T,B], as the reference's :854-860 (its one-hot line is commented out)
+                    if model.spaced_label_index is None:
+                        if model.pred is None:
+                            model.pred = model.hwr(image, None)
+                        model.spaced_label_index = model.take_alignment(label)
+                    got[name] = keep(model.spaced_label_index)
                 elif name == "gt":
                     got[name] = instance["gt"]
                 elif name == "author":
                     got[name] = instance["author"]
+                elif name == "name":
+                    got[name] = instance["name"]
                 elif name == "disc":
                     got[name] = predicted_disc
                 else:

@@ -567,6 +567,26 @@ int hwg_sheet_compose(const float* x, int B, int H, int W, int nrow, const float
 int hwg_sheet_row_means(const float* src, long long stride, int rows, int n, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Evaluation pictures of new_eval.py (evaluators/hwdataset_eval.py:141-262, there numpy and OpenCV on the host): per line the real line
+ * above its reconstruction, framed. image [B][1][H][Wi], recon [B][1][H][Wr] fp32 -> out [B][Hp][Wp][3] uint8, interleaved RGB,
+ * Wp = max(Wi, Wr), Hp = 2 H + 2 + S; S = hwg_eval_strip_rows() = 50 with a caption strip (codes != NULL), else 0.
+ * Level of a value x: v = 1 - (1 + x) / 2 in fp32, byte = trunc(clamp(v * 255, 0, 255)) - the fp32 product gives the exact product's byte for every v in [0, 1] -; NaN -> 0.
+ * The narrower input is centred (|Wi - Wr| / 2 columns of level 0 on its left, the rest on its right); pr / pg = that left padding of
+ * the real line / of the reconstruction. Rows 0..H-1 the real line, H and H+1 level 0, H+2..2H+1 the reconstruction.
+ * Real frame (0,255,0): rows 0 and H over columns [pr, Wp - pr), rows 0..H-1 at columns pr and Wp-1-pr.
+ * Reconstruction frame (0,0,255): rows H+1 and 2H+1 over [pg, Wp - pg), rows H+2..2H+1 at columns pg and Wp-1-pg.
+ * Strip: S rows of level 0 below; cell j of line b shows glyph codes[b * L + j] of atlas [G][gh][gw] (grey bytes) at columns
+ * 2 + j gw .., rows (S - gh) / 2 .. of the strip, clipped at Wp; a negative code (and a code >= G) leaves the cell empty. atlas and codes
+ * are device arrays; without a strip atlas, G, gh, gw, codes, L are NULL / 0.
+ * One launch writes EVERY byte of out, one aligned 32-bit store per lane; out_bytes: the bytes out holds, at least 3 B Hp Wp rounded up
+ * to 4; the bytes between the pictures' end and that bound are written 0, none beyond it is touched.
+ * Checked here before the launch: no NULL, sizes > 0, gh <= S, everything fits int, out_bytes, image / recon / codes / out 4-byte aligned.
+ * ------------------------------------------------------------------------------------------ */
+int hwg_eval_strip_rows(void);
+int hwg_eval_pairs(const float* image, const float* recon, int B, int H, int Wi, int Wr, const unsigned char* atlas, int G, int gh, int gw,
+                   const int* codes, int L, unsigned char* out, long long out_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Recognition error rates on the device (trainer/hw_with_style_trainer.py:894-914 getCER, utils/string_utils.py naive_decode,
  * utils/error_rates.py:2-26 cer / wer - there on the host, after downloading the whole prediction).
  * pred [T][B][C] fp32 (the recogniser's output as it stands); class_code [C] int32: the code point class c compares as (32 for every

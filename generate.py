@@ -1,8 +1,10 @@
 #!/usr/bin/env python
 """python generate.py -c checkpoint.pth -d out_dir [-g gpu] [-f config.json] [-a k=v,...] -s styles.pkl -r choice=R,num=N,text=...
 python generate.py -c checkpoint.pth -d out_dir -r choice=f,path1=a.png,path2=b.png,text=...
+python generate.py -c checkpoint.pth -d out_dir -s styles.pkl -r choice=u
 Non-interactive drop-in for the reference's generate.py flags: `R` writes N lines in styles sampled (and interpolated) from a style file,
-`f` interpolates between the styles of two line images in 20 steps. Lines are rendered in batches of equal label length, converted to
+`f` interpolates between the styles of two line images in 20 steps, `u` writes `deep` in the first 3 styles of every writer of a style
+file, with the ordered.txt that umap_styles.py reads. Lines are rendered in batches of equal label length, converted to
 8-bit grey and cut to their own width on the GPU, and written as PNGs by a thread pool - or, with --shard N, as lines_%05d.npz arrays of N
 lines each (pixels uint8 1-D, offsets int64 [n+1], widths int32 [n], index int64 [n]). The texts go to <savedir>/OUT.txt as `i:text`."""
 import argparse
@@ -19,7 +21,8 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 PANGRAM = "The quick brown fox jumps over the lazy dog."
-CHOICES = ("R", "f")
+CHOICES = ("R", "f", "u")
+PER_AUTHOR = 3                 # pictures per writer of the `u` action
 MAX_WRITERS = 16
 
 
@@ -195,6 +198,40 @@ def run_f(model, config, char_to_idx, run, args, gpu):
     return sink.count
 
 
+def run_u(model, config, char_to_idx, run, args, gpu):
+    """the reference's `u` action (generate.py:698-722): the text `deep` in the first PER_AUTHOR styles of every writer of the style file,
+    as <author>_<i>.png, and ordered.txt - the count per writer, then the file names, relative to the directory (the reference writes
+    the joined path, which umap_styles.py joins once more). Picture i of a writer is that writer's i-th style of the file(s). A writer with
+    fewer styles than that has no pictures (the reference stops with an IndexError there)."""
+    import umap_styles
+    from handwriting_line_generation_amd.generate import load_style_file, render_lines
+    if args.style_loc is None:
+        raise SystemExit("generate.py: choice=u renders the styles of a style file: pass -s path/to/styles.pkl")
+    if args.shard:
+        raise SystemExit("generate.py: choice=u writes the PNGs ordered.txt names; --shard does not apply")
+    names, styles = [], []
+    for author, rows in load_style_file(args.style_loc).items():
+        author = author.item() if isinstance(author, np.generic) else author
+        if len(rows) < PER_AUTHOR:
+            print("writer %s has %d styles, fewer than %d: no pictures" % (author, len(rows), PER_AUTHOR), flush=True)
+            continue
+        for i in range(PER_AUTHOR):
+            names.append(umap_styles.picture_name(author, i))
+            styles.append(np.asarray(rows[i], dtype=np.float32).reshape(-1))
+    if not names:
+        raise SystemExit("generate.py: no writer of %s has %d styles" % (args.style_loc, PER_AUTHOR))
+    sink = LineSink(args.savedir, "%s", 0, args.writers)
+    try:
+        for i, line in render_lines(model, ["deep"] * len(names), np.stack(styles), char_to_idx, gpu, batch_lines=args.batch):
+            sink.add(names[i], line)
+    finally:
+        sink.close()
+    if sink.count != len(names):
+        raise SystemExit("generate.py: the character set of this checkpoint cannot write 'deep'")
+    umap_styles.write_ordered(args.savedir, PER_AUTHOR, names)
+    return sink.count
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="MI355X-native handwriting line generation from a checkpoint")
     ap.add_argument("-c", "--checkpoint", type=str, default=None, help="checkpoint of this package or of the reference")
@@ -216,8 +253,9 @@ def main(argv=None):
     run = parse_run(args.run)
     choice = run.get("choice", "")
     if choice not in CHOICES:
-        raise NotImplementedError("generate.py: action %r is not built; the two that exist are 'R' (random interpolated styles from a style "
-                                  "file) and 'f' (interpolation between the styles of two line images)" % choice)
+        raise NotImplementedError("generate.py: action %r is not built; the three that exist are 'R' (random interpolated styles from a style "
+                                  "file), 'f' (interpolation between the styles of two line images) and 'u' (the pictures umap_styles.py "
+                                  "pastes into its map)" % choice)
     if args.checkpoint is None:
         raise SystemExit("generate.py: must provide a checkpoint (with -c)")
     if args.savedir is None:
@@ -237,8 +275,10 @@ def main(argv=None):
     t0 = time.time()
     if choice == "R":
         n = run_R(model, config, char_to_idx, run, args, rand, gpu)
-    else:
+    elif choice == "f":
         n = run_f(model, config, char_to_idx, run, args, gpu)
+    else:
+        n = run_u(model, config, char_to_idx, run, args, gpu)
     torch.cuda.synchronize()
     dt = time.time() - t0
     print("lines %d  seconds %.3f  lines/s %.1f" % (n, dt, n / dt if dt > 0 else 0.0), flush=True)

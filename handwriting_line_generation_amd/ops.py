@@ -2693,6 +2693,82 @@ def writer_first_rank(styles, author_ids, metric, out=None):
 
 
 # ----------------------------------------------------------------------------------------------
+# style-space map: exact k nearest rows and the layout epochs over the fuzzy graph (csrc/style_map.hip)
+# ----------------------------------------------------------------------------------------------
+KNN_MAX_K = 64
+
+
+def knn_rows(styles, k, out=None):
+    """styles [N, D] fp32 on the device -> (idx int32 [N, k], d2 fp32 [N, k]): per row the k nearest other rows, ascending by
+    (squared L2 distance, column); the row itself is left out by index. `out`: an (idx, d2) pair to write into."""
+    if not torch.is_tensor(styles) or styles.dim() != 2 or not styles.is_cuda or styles.dtype != torch.float32 or not styles.is_contiguous():
+        raise L.HwgError("knn_rows: styles must be a contiguous [N, D] fp32 device tensor, got %s %s" % (
+            tuple(styles.shape) if torch.is_tensor(styles) else type(styles), getattr(styles, "dtype", None)))
+    N, D = styles.shape
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= KNN_MAX_K or k > N - 1:
+        raise L.HwgError("knn_rows: k must be an integer in 1..%d and at most N - 1 = %d, got %r" % (KNN_MAX_K, N - 1, k))
+    if out is None:
+        idx = torch.empty((N, k), dtype=torch.int32, device=styles.device)
+        d2 = torch.empty((N, k), dtype=torch.float32, device=styles.device)
+    else:
+        idx, d2 = out
+        if tuple(idx.shape) != (N, k) or idx.dtype != torch.int32 or not idx.is_contiguous() or tuple(d2.shape) != (N, k) or \
+                d2.dtype != torch.float32 or not d2.is_contiguous() or idx.device != styles.device or d2.device != styles.device:
+            raise L.HwgError("knn_rows: out must be contiguous (int32 [%d, %d], fp32 [%d, %d]) tensors on %s" % (N, k, N, k, styles.device))
+    L.call("hwg_knn_rows", styles, N, D, k, idx, d2, _stream())
+    return idx, d2
+
+
+class UmapGraph:
+    """a checked graph on the device: row_ptr int32 [N + 1], col int32 [E], period_q int32 [E]"""
+
+    def __init__(self, row_ptr, col, period_q, n, e):
+        self.row_ptr, self.col, self.period_q, self.n, self.e = row_ptr, col, period_q, n, e
+
+
+def umap_graph(row_ptr, col, period_q, device):
+    """host arrays of a CSR graph -> UmapGraph on `device`. Checked here, before the upload, because the kernel follows these numbers into
+    memory: row_ptr [N + 1] starts at 0, never decreases and ends at E = len(col) >= 1; 0 <= col < N; period_q >= 1."""
+    import numpy as np
+    row_ptr, col, period_q = (np.asarray(x) for x in (row_ptr, col, period_q))
+    for name, x in (("row_ptr", row_ptr), ("col", col), ("period_q", period_q)):
+        if x.ndim != 1 or x.dtype.kind not in "iu":
+            raise L.HwgError("umap_graph: %s must be a 1-D integer array, got %s %s" % (name, x.shape, x.dtype))
+    n, e = row_ptr.shape[0] - 1, col.shape[0]
+    if n < 1 or n > 1 << 20 or e < 1 or e >= 1 << 31 or period_q.shape[0] != e:
+        raise L.HwgError("umap_graph: bad sizes N=%d (1..2^20) E=%d (1..2^31-1) with %d periods" % (n, e, period_q.shape[0]))
+    if int(row_ptr[0]) != 0 or int(row_ptr[-1]) != e or (np.diff(row_ptr.astype(np.int64)) < 0).any():
+        raise L.HwgError("umap_graph: row_ptr must rise from 0 to E=%d without a step down" % e)
+    if int(col.min()) < 0 or int(col.max()) >= n:
+        raise L.HwgError("umap_graph: col must lie in 0..%d, got %d..%d" % (n - 1, int(col.min()), int(col.max())))
+    if int(period_q.min()) < 1 or int(period_q.max()) >= 1 << 31:
+        raise L.HwgError("umap_graph: period_q must lie in 1..2^31-1, got %d..%d" % (int(period_q.min()), int(period_q.max())))
+    up = [h2d(np.array(x, dtype=np.int32), device) for x in (row_ptr, col, period_q)]
+    return UmapGraph(up[0], up[1], up[2], n, e)
+
+
+def umap_layout(graph, y, n_epochs, a, b, neg, seed, epoch_begin=0, epoch_end=None, scratch=None):
+    """the layout epochs epoch_begin + 1 .. epoch_end (default: n_epochs) of n_epochs over `graph` (umap_graph), in place in y fp32 [N, 2]
+    on the device; `scratch`: a second [N, 2] buffer (allocated when None). One launch per epoch; returns y."""
+    if not isinstance(graph, UmapGraph):
+        raise L.HwgError("umap_layout: graph must come from ops.umap_graph, got %s" % type(graph))
+    if not torch.is_tensor(y) or tuple(y.shape) != (graph.n, 2) or not y.is_cuda or y.dtype != torch.float32 or not y.is_contiguous() or \
+            y.device != graph.col.device:
+        raise L.HwgError("umap_layout: y must be a contiguous [%d, 2] fp32 tensor on %s, got %s %s" % (
+            graph.n, graph.col.device, tuple(y.shape) if torch.is_tensor(y) else type(y), getattr(y, "dtype", None)))
+    if scratch is None:
+        scratch = torch.empty_like(y)
+    elif not torch.is_tensor(scratch) or tuple(scratch.shape) != (graph.n, 2) or scratch.dtype != torch.float32 or \
+            not scratch.is_contiguous() or scratch.device != y.device or scratch.data_ptr() == y.data_ptr():
+        raise L.HwgError("umap_layout: scratch must be another contiguous [%d, 2] fp32 tensor on %s" % (graph.n, y.device))
+    if epoch_end is None:
+        epoch_end = n_epochs
+    L.call("hwg_umap_layout", graph.row_ptr, graph.col, graph.period_q, graph.n, graph.e, y, scratch, int(epoch_begin), int(epoch_end),
+           int(n_epochs), float(a), float(b), int(neg), int(seed) & (2 ** 64 - 1), _stream())
+    return y
+
+
+# ----------------------------------------------------------------------------------------------
 # frozen BatchNorm (eval) and the FusedUpsample weight transform
 # ----------------------------------------------------------------------------------------------
 def norm_apply_frozen(x, running_mean, running_var, eps, gamma, beta, act=ACT_NONE, slope=0.0):

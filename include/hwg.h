@@ -641,6 +641,30 @@ int hwg_lstm_bwd(const float* dy, const float* gates, const float* c, const floa
                  void* stream);
 int hwg_lstm_pack_whh(const float* whh_f, const float* whh_r, int H, float* whh_t, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The style-space map of umap_styles.py (csrc/style_map.hip; reference umap_styles.py:105-110 - there umap-learn on the host).
+ * hwg_knn_rows: styles [N][D] fp32 -> idx [N][K] int32, d2 [N][K] fp32: per row the K nearest OTHER rows (the row's own column is excluded
+ * by index, an exact duplicate is a neighbour at distance 0), ascending by the key (d2, column); d2 = sum (a - b)^2 as one fp32 chain
+ * fma(diff, diff, acc) over d ascending, the bits of hwg_writer_first_rank's squared L2. One launch, no workspace, nothing N x N.
+ * Checked before the launch: no NULL, D >= 1, 1 <= K <= 64, K <= N - 1, N <= 2^20, D <= 65536, styles 16-byte, idx and d2 4-byte aligned.
+ *
+ * hwg_umap_layout: the layout epochs n = epoch_begin + 1 .. epoch_end of n_epochs over a graph in CSR form (row_ptr [N+1], col [E],
+ * period_q [E] int32: edge e is drawn in epoch n iff (n * 65536) / period_q[e] > ((n - 1) * 65536) / period_q[e], integer division).
+ * y [N][2] fp32 holds the positions before and after; y_scratch [N][2] is the second buffer: one launch per epoch reads one and writes
+ * the other (an odd number of epochs starts with a copy), so epochs 0..2 then 2..5 leave the bytes of 0..5.
+ * Epoch n, vertex i, all positions those at the start of the epoch, alpha = (float)(1 - (n - 1) / (double) n_epochs): per drawn edge e
+ * (j = col[e]) the attraction 2 clamp(c (y_i - y_j), -4, 4) with c = -2 a b s^(b-1) / (a s^b + 1), s = |y_i - y_j|^2 (nothing if s = 0),
+ * then for t = 0 .. neg-1 the repulsion from r = (word * N) >> 32, word = philox4x32-10(seed, (n E + e) ceil(neg / 4) + t / 4)[t % 4]:
+ * nothing if r == i, else clamp(c (y_i - y_r), -4, 4) with c = 2 b / ((0.001 + s)(a s^b + 1)), (4, 4) if s = 0;
+ * y_i' = y_i + alpha * sum (fp32, in the fixed order stated at the top of csrc/style_map.hip).
+ * Checked before any launch: no NULL, y != y_scratch, N <= 2^20, E >= 1, 1 <= neg <= 16, 1 <= n_epochs <= 32767 (a period is at most
+ * 65536 n_epochs), 0 <= epoch_begin <= epoch_end <= n_epochs, a, b positive and finite, y and y_scratch 8-byte aligned. What lies in
+ * device memory - row_ptr monotone from 0 to E, 0 <= col < N, period_q >= 1 - is the caller's to check (ops.umap_graph does).
+ * ------------------------------------------------------------------------------------------ */
+int hwg_knn_rows(const float* styles, int N, int D, int K, int* idx, float* d2, void* stream);
+int hwg_umap_layout(const int* row_ptr, const int* col, const int* period_q, int N, int E, float* y, float* y_scratch, int epoch_begin,
+                    int epoch_end, int n_epochs, float a, float b, int neg, unsigned long long seed, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

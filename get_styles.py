@@ -1,11 +1,13 @@
 #!/usr/bin/env python
-"""python get_styles.py -c checkpoint.pth -d out_dir [-g gpu] [-b batch] [-f config.json] [-a k=v,...] [-T] [--cer] [--writer-id]
+"""python get_styles.py -c checkpoint.pth -d out_dir [-g gpu] [-b batch] [-f config.json] [-a k=v,...] [-T] [--cer] [--writer-id] [--distances]
 The reference's get_styles.py: the style vector of every line of the training and validation splits (with -T: of the test split), written
 as <savedir>/train_styles_<iteration>.pkl and val_styles_<iteration>.pkl (test_styles_<iteration>.pkl): {"styles": float32 [n, style_dim],
 "authors": array [n]} - what `generate.py -s` samples from. Only the model is built (no trainer, no optimizer). With --cer the recogniser's
 error rates on the real lines and on the same texts rendered in their own extracted style are counted on the GPU on the way and written to
 <split>_cer_<iteration>.json. With --writer-id the written styles are scored for writer retrieval (evaluate.writer_id with dedupe: top-1 / 5 / 20
-under L1 and squared L2, what eval_writer_id.py --dedupe prints) into <split>_writer_id_<iteration>.json."""
+under L1 and squared L2, what eval_writer_id.py --dedupe prints) into <split>_writer_id_<iteration>.json. With --distances their same-writer and
+different-writer distances (evaluate.style_distances with dedupe, without the writer x writer matrices: pairs, mean, std and the two histograms,
+what play_styles.py --dedupe prints) go into <split>_distances_<iteration>.json."""
 import argparse
 import json
 import os
@@ -30,6 +32,8 @@ def parse_args(argv=None):
     ap.add_argument("--cer", action="store_true", help="also score the recogniser on real and regenerated lines: <split>_cer_<iteration>.json")
     ap.add_argument("--writer-id", dest="writer_id", action="store_true",
                     help="also score the written styles for writer retrieval: <split>_writer_id_<iteration>.json")
+    ap.add_argument("--distances", action="store_true",
+                    help="also measure same-writer against different-writer style distances: <split>_distances_<iteration>.json")
     return ap.parse_args(argv)
 
 
@@ -106,6 +110,14 @@ def main(argv=None):
                 json.dump(scores, f)
             print("saved %s  lines %d (dropped %d)  l2 top1 %.4f top5 %.4f top20 %.4f" % (
                 loc, scores["lines"], scores["dropped"], scores["l2"]["top1"], scores["l2"]["top5"], scores["l2"]["top20"]), flush=True)
+        if args.distances:
+            loc = os.path.join(args.savedir, "%s_distances_%s.json" % (name, iteration))
+            dist = evaluate.style_distances(result["styles"], result["authors"], gpu, dedupe=True, matrices=False)
+            with open(loc, "w") as f:
+                json.dump(dist, f)
+            print("saved %s  lines %d (dropped %d)  same writer: pairs %d mean %s  different writers: pairs %d mean %s" % (
+                loc, dist["lines"], dist["dropped"], dist["same"]["pairs"], dist["same"]["mean"], dist["different"]["pairs"],
+                dist["different"]["mean"]), flush=True)
         n = len(result["authors"])
         print("%s: lines %d  seconds %.3f  lines/s %.1f" % (name, n, dt, n / dt if dt > 0 else 0.0), flush=True)
 

@@ -171,6 +171,14 @@ static inline int hwg_stream_grid(long long work_items, int block) {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
+// The one place a style-distance term is added (writer_id.hip, style_map.hip, style_pairs.hip): a distance is one fp32 chain of these steps
+// over d = 0 .. D-1 ascending, so it is the same bits in whichever kernel, tile position or lane it is computed. METRIC 0: L1, 1: squared L2.
+template <int METRIC>
+__device__ __forceinline__ float hwg_dist_step(float acc, float a, float b) {
+  const float diff = a - b;
+  return METRIC ? fmaf(diff, diff, acc) : acc + fabsf(diff);
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -75,10 +75,7 @@ __global__ __launch_bounds__(SM_BLOCK) void sm_knn_kernel(const float* __restric
 #pragma unroll
         for (int r = 0; r < 4; ++r)
 #pragma unroll
-          for (int c = 0; c < 4; ++c) {
-            const float diff = rv[r] - cv[c];                                 // the distance step of writer_id.hip (squared L2)
-            acc[r][c] = fmaf(diff, diff, acc[r][c]);
-          }
+          for (int c = 0; c < 4; ++c) acc[r][c] = hwg_dist_step<1>(acc[r][c], rv[r], cv[c]);   // the distance step of writer_id.hip (squared L2)
       }
     }
 

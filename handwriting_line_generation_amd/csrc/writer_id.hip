@@ -33,12 +33,10 @@ constexpr int WID_TILE_FLOATS = WID_DK * (WID_RS + WID_CS);
 constexpr int WID_MERGE_FLOATS = 6 * WID_BR * WID_SHARERS;
 constexpr int WID_LDS_FLOATS = WID_TILE_FLOATS > WID_MERGE_FLOATS ? WID_TILE_FLOATS : WID_MERGE_FLOATS;
 
-// the one place a distance term is added (both sweeps, both tiles of a pair, every lane)
+// the one place a distance term is added (both sweeps, both tiles of a pair, every lane): hwg_common.h's step, shared with the other
+// style-distance kernels
 template <int METRIC>
-__device__ __forceinline__ float wid_accumulate(float acc, float a, float b) {
-  const float diff = a - b;
-  return METRIC ? fmaf(diff, diff, acc) : acc + fabsf(diff);
-}
+__device__ __forceinline__ float wid_accumulate(float acc, float a, float b) { return hwg_dist_step<METRIC>(acc, a, b); }
 
 __device__ __forceinline__ bool wid_below(float d, int c, float d2, int c2) { return d < d2 || (d == d2 && c < c2); }
 

@@ -211,3 +211,106 @@ def writer_id(styles, authors, gpu, tops=(1, 5, 20), dedupe=False):
         part["rows_without_match"] = int((~has).sum())
         out[name] = part
     return {k: out[k] for k in ("lines", "dim", "writers", "dropped", "l1", "l2") if k in out}
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# separation of a style space (reference play_styles.py: are two lines of one writer closer than two lines of two writers?)
+PAIR_MATRIX_WRITERS = 4096      # the writers x writers matrices are left out above this many writers (ops.SP_MAX_WRITERS)
+
+
+def pair_summary(count, total, total_sq):
+    """count, sum of d and sum of d^2 of a set of distances -> {"pairs", "mean", "std"}: std the population standard deviation (np.std),
+    0 for a single pair, mean and std None for no pair. fp64 on the host."""
+    n = int(count)
+    if n == 0:
+        return {"pairs": 0, "mean": None, "std": None}
+    mean = float(total) / n
+    var = float(total_sq) / n - mean * mean
+    return {"pairs": n, "mean": mean, "std": float(np.sqrt(var)) if n > 1 and var > 0 else 0.0}
+
+
+def pair_edges(min_d2, max_d2, bins):
+    """-> (edges fp64 [bins + 1], edge2 fp32 [bins + 1]): `bins` equal-width bins in d from sqrt(min_d2) to sqrt(max_d2); edge2 the edges
+    squared in fp64 and rounded to fp32 once, the first then 0 and the last +inf (what the kernel compares d^2 with)"""
+    edges = np.linspace(np.sqrt(np.float64(min_d2)), np.sqrt(np.float64(max_d2)), bins + 1)
+    edge2 = (edges * edges).astype(np.float32)
+    edge2[0], edge2[-1] = 0.0, np.inf
+    return edges, edge2
+
+
+def pair_matrices(count, total, total_sq):
+    """[A, A] count / sum / sumsq -> (pair_count int64, pair_mean, pair_std fp64): NaN where a cell has no pair, std 0 where it has one"""
+    count = np.asarray(count, dtype=np.int64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean = np.asarray(total, dtype=np.float64) / count
+        var = np.asarray(total_sq, dtype=np.float64) / count - mean * mean
+        std = np.sqrt(np.maximum(var, 0.0))
+    std[count == 1] = 0.0
+    mean[count == 0] = np.nan
+    std[count == 0] = np.nan
+    return count, mean, std
+
+
+def style_distances(styles, authors, gpu, dedupe=False, matrices=True, bins=64):
+    """Same-writer and different-writer distances of a style space: styles numpy [n, D] or [n, D, 1, 1], authors a sequence of n. Over all
+    pairs of lines, d = sqrt(sum (a - b)^2) (the sum in fp32 as evaluate.writer_id's l2, the root and everything after it in fp64). ->
+    {"lines", "dim", "writers", "same": {"pairs", "mean", "std"}, "different": {...}, "hist": {"edges", "same", "different"}} - std the
+    population standard deviation, mean and std None without a pair; the histograms over `bins` equal-width bins in d between the
+    smallest and the largest distance (edges [bins + 1]; empty lists without a pair) -, with dedupe "dropped" (as writer_id), with
+    matrices "writer_names" [A] (order of first appearance) and numpy [A, A] "pair_count", "pair_mean", "pair_std" (NaN where two writers
+    have no pair, i.e. the diagonal cell of a single-line writer; std 0 for one pair); above 4096 writers the matrices are left out with
+    a printed note. Rows are sorted by writer for the device (stable); the order of the input shows in no result. Two device calls
+    (ops.style_pair_stats): the sums, then the histogram between the extremes the first call found; nothing of size n x n is stored."""
+    import math
+    styles = np.asarray(styles)
+    if styles.ndim == 4 and styles.shape[2:] == (1, 1):
+        styles = styles[:, :, 0, 0]
+    if styles.ndim != 2 or styles.shape[0] < 1 or styles.shape[1] < 1:
+        raise ValueError("style_distances: styles must be [n, D] or [n, D, 1, 1] with n, D >= 1, got %s" % (tuple(styles.shape),))
+    styles = np.ascontiguousarray(styles, dtype=np.float32)
+    if len(authors) != styles.shape[0]:
+        raise ValueError("style_distances: %d authors for %d styles" % (len(authors), styles.shape[0]))
+    finite = np.isfinite(styles).all(axis=1)
+    if not finite.all():
+        raise ValueError("style_distances: style row %d is not finite" % int(np.argmin(finite)))
+    if isinstance(bins, bool) or not isinstance(bins, int) or not 1 <= bins <= ops.SP_MAX_BINS:
+        raise ValueError("style_distances: bins must be an integer in 1..%d, got %r" % (ops.SP_MAX_BINS, bins))
+    ids, writers = author_ids(authors)
+    names = [None] * writers
+    for a, i in zip(authors, ids.tolist()):
+        if names[i] is None:
+            names[i] = a.item() if isinstance(a, np.generic) else a
+    out = {}
+    if dedupe:
+        keep = dedupe_rows(styles, ids)                       # (a writer's first row always stays: the ids stay 0 .. writers - 1)
+        out["dropped"] = int((~keep).sum())
+        styles, ids = styles[keep], ids[keep]
+    order = np.argsort(ids, kind="stable")
+    styles, ids = np.ascontiguousarray(styles[order]), np.ascontiguousarray(ids[order])
+    n, dim = styles.shape
+    out.update(lines=n, dim=dim, writers=writers)
+    if matrices and writers > PAIR_MATRIX_WRITERS:
+        print("style_distances: %d writers, the writers x writers matrices are left out above %d" % (writers, PAIR_MATRIX_WRITERS))
+        matrices = False
+    styles_d, ids_d = ops.h2d(styles, gpu), ops.h2d(ids, gpu)
+    count, total, total_sq, d2_range, _ = ops.style_pair_stats(styles_d, ids_d, ops.SP_WRITER_PAIRS if matrices else ops.SP_SAME_DIFFERENT)
+    count, total, total_sq, d2_range = (t.cpu().numpy() for t in (count, total, total_sq, d2_range))
+    if matrices:
+        upper = np.triu(np.ones((writers, writers), dtype=bool), 1)
+        cells = {"same": np.eye(writers, dtype=bool), "different": upper}
+        for name, mask in cells.items():                      # the cells a <= b, each once; fsum: the exactly rounded sum, whatever the order
+            out[name] = pair_summary(count[mask].sum(dtype=np.int64), math.fsum(total[mask].tolist()), math.fsum(total_sq[mask].tolist()))
+    else:
+        out["same"] = pair_summary(count[0], total[0], total_sq[0])
+        out["different"] = pair_summary(count[1], total[1], total_sq[1])
+    if out["same"]["pairs"] + out["different"]["pairs"] == 0:
+        out["hist"] = {"edges": [], "same": [], "different": []}
+    else:
+        edges, edge2 = pair_edges(d2_range[0], d2_range[1], bins)
+        hist = ops.style_pair_stats(styles_d, ids_d, ops.SP_SAME_DIFFERENT, edge2=edge2)[4].cpu().numpy()
+        out["hist"] = {"edges": edges.tolist(), "same": hist[0].tolist(), "different": hist[1].tolist()}
+    if matrices:
+        out["writer_names"] = names
+        out["pair_count"], out["pair_mean"], out["pair_std"] = pair_matrices(count, total, total_sq)
+    keys = ("lines", "dim", "writers", "dropped", "same", "different", "hist", "writer_names", "pair_count", "pair_mean", "pair_std")
+    return {k: out[k] for k in keys if k in out}

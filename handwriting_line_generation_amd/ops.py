@@ -2769,6 +2769,75 @@ def umap_layout(graph, y, n_epochs, a, b, neg, seed, epoch_begin=0, epoch_end=No
 
 
 # ----------------------------------------------------------------------------------------------
+# same-writer / different-writer distances over all pairs of style vectors (csrc/style_pairs.hip)
+# ----------------------------------------------------------------------------------------------
+SP_SAME_DIFFERENT, SP_WRITER_PAIRS = 0, 1               # hwg_style_pair_stats's mode: two cells, writers x writers cells
+SP_MAX_WRITERS, SP_MAX_BINS = 4096, 256                 # mode 1's limit on the writers, the histogram's on the bins
+
+
+def style_pair_stats(styles, writer, mode, edge2=None, out=None, workspace=None):
+    """styles [N, D] fp32 and writer [N] int32 on the device, the rows ordered so that writer (values 0 .. A-1, A = writer[-1] + 1) never
+    decreases -> (count int64, sum fp64, sumsq fp64, d2_range fp32 [2], hist int64 [2, bins] or None) over the pairs i < j: number of
+    pairs, sum of the distances and sum of their squares per cell - mode 0: [2], the pairs of one writer and the pairs of two; mode 1:
+    [A, A], one cell per pair of writers, mirrored -, the smallest and largest squared distance (+inf, -inf without a pair), and with
+    edge2 (fp32 [bins + 1], ascending, squared edges; a device tensor or a host array) the histograms of the one-writer and of the
+    two-writer pairs. `out`: the tuple of tensors to write into (hist last, only with edge2); `workspace`: a uint8 device tensor of at
+    least hwg_style_pair_stats_workspace bytes (allocated when None). The order of writer is checked here, on a host copy."""
+    import numpy as np
+    if not torch.is_tensor(styles) or styles.dim() != 2 or styles.dtype != torch.float32 or not styles.is_contiguous() or \
+            styles.shape[0] < 1 or styles.shape[1] < 1:
+        raise L.HwgError("style_pair_stats: styles must be a contiguous [N, D] fp32 device tensor, got %s %s" % (
+            tuple(styles.shape) if torch.is_tensor(styles) else type(styles), getattr(styles, "dtype", None)))
+    N, D = styles.shape
+    if not torch.is_tensor(writer) or tuple(writer.shape) != (N,) or writer.dtype != torch.int32 or writer.device != styles.device or \
+            not writer.is_contiguous():
+        raise L.HwgError("style_pair_stats: writer must be a contiguous [%d] int32 tensor on %s, got %s %s" % (
+            N, styles.device, tuple(writer.shape) if torch.is_tensor(writer) else type(writer), getattr(writer, "dtype", None)))
+    if mode not in (SP_SAME_DIFFERENT, SP_WRITER_PAIRS):
+        raise L.HwgError("style_pair_stats: mode must be 0 (same / different) or 1 (writers x writers), got %r" % (mode,))
+    w = writer.cpu().numpy()
+    if int(w[0]) < 0 or (np.diff(w.astype(np.int64)) < 0).any():
+        raise L.HwgError("style_pair_stats: writer must start at 0 or above and never decrease (sort the rows by writer first)")
+    A = int(w[-1]) + 1
+    if A > N:
+        raise L.HwgError("style_pair_stats: writer ids reach %d with %d rows: number the writers 0 .. A-1" % (A - 1, N))
+    if mode == SP_WRITER_PAIRS and A > SP_MAX_WRITERS:
+        raise L.HwgError("style_pair_stats: %d writers, the writers x writers mode takes at most %d" % (A, SP_MAX_WRITERS))
+    bins = 0
+    if edge2 is not None:
+        e = edge2.detach().cpu().numpy() if torch.is_tensor(edge2) else np.asarray(edge2)
+        if e.ndim != 1 or e.dtype != np.float32 or not 1 <= e.shape[0] - 1 <= SP_MAX_BINS or np.isnan(e).any() or (np.diff(e) < 0).any():
+            raise L.HwgError("style_pair_stats: edge2 must be fp32 [bins + 1] with 1 <= bins <= %d, ascending, without NaN, got %s %s" % (
+                SP_MAX_BINS, e.shape, e.dtype))
+        bins = e.shape[0] - 1
+        if not torch.is_tensor(edge2) or edge2.device != styles.device or not edge2.is_contiguous():
+            edge2 = h2d(np.ascontiguousarray(e), styles.device)
+    if not styles.is_cuda:
+        raise L.HwgError("style_pair_stats: styles must be on a GPU, got %s" % (styles.device,))
+    cells = (2,) if mode == SP_SAME_DIFFERENT else (A, A)
+    want = [(cells, torch.int64), (cells, torch.float64), (cells, torch.float64), ((2,), torch.float32)] + ([((2, bins), torch.int64)] if bins else [])
+    if out is None:
+        out = tuple(torch.empty(shape, dtype=dtype, device=styles.device) for shape, dtype in want)
+    else:
+        out = tuple(out)
+        if len(out) != len(want) or any(not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or
+                                        t.device != styles.device for t, (shape, dtype) in zip(out, want)):
+            raise L.HwgError("style_pair_stats: out must be contiguous tensors on %s of %s" % (
+                styles.device, ", ".join("%s %s" % (dtype, list(shape)) for shape, dtype in want)))
+    need = int(L.query("hwg_style_pair_stats_workspace", N, A, int(mode)))
+    if need == 0:
+        raise L.HwgError("style_pair_stats: N=%d A=%d mode=%d is beyond what the kernel takes" % (N, A, mode))
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.uint8, device=styles.device)
+    elif not torch.is_tensor(workspace) or workspace.dtype != torch.uint8 or workspace.dim() != 1 or not workspace.is_contiguous() or \
+            workspace.device != styles.device or workspace.numel() < need:
+        raise L.HwgError("style_pair_stats: workspace must be a contiguous uint8 tensor of at least %d bytes on %s" % (need, styles.device))
+    L.call("hwg_style_pair_stats", styles, writer, N, D, A, int(mode), edge2, bins, out[0], out[1], out[2], out[3], out[4] if bins else None,
+           workspace, workspace.numel(), _stream())
+    return out if bins else out + (None,)
+
+
+# ----------------------------------------------------------------------------------------------
 # frozen BatchNorm (eval) and the FusedUpsample weight transform
 # ----------------------------------------------------------------------------------------------
 def norm_apply_frozen(x, running_mean, running_var, eps, gamma, beta, act=ACT_NONE, slope=0.0):

@@ -665,6 +665,35 @@ int hwg_knn_rows(const float* styles, int N, int D, int K, int* idx, float* d2, 
 int hwg_umap_layout(const int* row_ptr, const int* col, const int* period_q, int N, int E, float* y, float* y_scratch, int epoch_begin,
                     int epoch_end, int n_epochs, float a, float b, int neg, unsigned long long seed, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Same-writer / different-writer distances in style space (csrc/style_pairs.hip; reference play_styles.py:19-39 - there a double Python
+ * loop over all N (N - 1) / 2 pairs and three Python lists of that length - and :43-53, the writer x writer mean / std matrices behind
+ * its exit(), keyed by line where a writer was meant).
+ * styles [N][D] fp32 with the rows ordered so that writer [N] int32 (values 0 .. A-1) never decreases. Per unordered pair i < j:
+ * d2 = sum (a - b)^2 as one fp32 chain fma(diff, diff, acc) over d ascending (the bits of hwg_writer_first_rank's metric 1 and of
+ * hwg_knn_rows), d = sqrt((double) d2). Per cell: count int64, sum of d and sumsq of (double) d2 in fp64, in a fixed order.
+ *   mode 0: count, sum, sumsq [2]: cell 0 the pairs of one writer, cell 1 the pairs of two writers.
+ *   mode 1: count, sum, sumsq [A][A]: cell (a, b) the pairs with one line of writer a and one of writer b ((a, a): both of a); (b, a)
+ *           holds the same numbers as (a, b); a cell without pairs is (0, 0.0, 0.0).
+ * d2_range [2] fp32: the smallest and the largest d2 over all pairs (+inf, -inf when N == 1).
+ * edge2 [bins + 1] fp32 ascending with hist [2][bins] int64 (both or neither; neither: bins == 0): hist[0] over the pairs of one writer,
+ * hist[1] over the pairs of two; a pair is counted in bin k iff edge2[k] <= d2 < edge2[k + 1], compared in fp32 on the bits of d2; pairs
+ * below edge2[0], at or above edge2[bins] or with a NaN d2 are in no bin.
+ * Every entry of every output is written; two calls on the same input give the same bits. Nothing N x N is stored, no floating-point
+ * atomics (the histogram's counters are integer atomics), nothing crosses a workgroup inside a launch: mode 0 is two launches (sweep over
+ * the upper triangle, reduce), mode 1 four (writer bounds, sweep, range, cells); with a histogram one memset in front.
+ * workspace: hwg_style_pair_stats_workspace(N, A, mode) bytes (0 for sizes the entry point refuses), 16-byte aligned, contents ignored.
+ * Checked here before any launch: no NULL (edge2 / hist excepted, as a pair), N, D >= 1, 1 <= A <= N, mode 0 or 1, 1 <= bins <= 256 with
+ * edge2, N <= 2^20, D <= 65536, A <= 4096 in mode 1, styles and workspace 16-byte, count / sum / sumsq / hist 8-byte, writer / edge2 /
+ * d2_range 4-byte aligned, workspace_bytes large enough. What lies in device memory is the caller's to check (ops.style_pair_stats does,
+ * on the host): writer non-decreasing within 0 .. A-1, edge2 ascending. The kernels stay inside their buffers whatever it holds (ids
+ * outside 0 .. A-1 are dropped), but the sums of an unsorted writer array mean nothing.
+ * ------------------------------------------------------------------------------------------ */
+size_t hwg_style_pair_stats_workspace(int N, int A, int mode);
+int hwg_style_pair_stats(const float* styles, const int* writer, int N, int D, int A, int mode, const float* edge2, int bins,
+                         long long* count, double* sum, double* sumsq, float* d2_range, long long* hist, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,9 +2,15 @@
 """python generate.py -c checkpoint.pth -d out_dir [-g gpu] [-f config.json] [-a k=v,...] -s styles.pkl -r choice=R,num=N,text=...
 python generate.py -c checkpoint.pth -d out_dir -r choice=f,path1=a.png,path2=b.png,text=...
 python generate.py -c checkpoint.pth -d out_dir -s styles.pkl -r choice=u
+python generate.py -c checkpoint.pth -d out_dir [-T] -r choice=s[,batch=i]
+python generate.py -c checkpoint.pth -d out_dir [-T] -r choice=r,num_styles=K,step=0.1[,text=...][,start=i,stride=n]
+python generate.py -c checkpoint.pth -d out_dir [-T] -r choice=A,author=<id>[,text=...][,max=5]
 Non-interactive drop-in for the reference's generate.py flags: `R` writes N lines in styles sampled (and interpolated) from a style file,
 `f` interpolates between the styles of two line images in 20 steps, `u` writes `deep` in the first 3 styles of every writer of a style
-file, with the ordered.txt that umap_styles.py reads. Lines are rendered in batches of equal label length, converted to
+file, with the ordered.txt that umap_styles.py reads. The actions behind the paper's figures read the validation split of the checkpoint's
+dataset (-T: the test split), one writer per batch: `s` renders batch i 79 times while its character spacing is stretched and squeezed
+(gen<b>_<i>.png), `r` walks in a closed loop through the styles of K writers (gen<b>_<i>.png, styles<b>.pth), `A` writes a text in the mean
+style of one writer's lines (gen_<author>.png). Lines are rendered in batches of equal label length, converted to
 8-bit grey and cut to their own width on the GPU, and written as PNGs by a thread pool - or, with --shard N, as lines_%05d.npz arrays of N
 lines each (pixels uint8 1-D, offsets int64 [n+1], widths int32 [n], index int64 [n]). The texts go to <savedir>/OUT.txt as `i:text`."""
 import argparse
@@ -21,7 +27,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 PANGRAM = "The quick brown fox jumps over the lazy dog."
-CHOICES = ("R", "f", "u")
+CHOICES = ("R", "f", "u", "s", "r", "A")
 PER_AUTHOR = 3                 # pictures per writer of the `u` action
 MAX_WRITERS = 16
 
@@ -232,6 +238,113 @@ def run_u(model, config, char_to_idx, run, args, gpu):
     return sink.count
 
 
+def dataset_loader(config, test):
+    """the loader the reference's dataset actions iterate (generate.py:140-156): one writer per batch (batch_size 1) of the validation
+    split, or with -T of the test split with one line per batch (a_batch_size 1)"""
+    from handwriting_line_generation_amd.data.author_hw_dataset import getDataLoader
+    dl = config["data_loader"]
+    val = config.setdefault("validation", {})
+    dl["batch_size"] = val["batch_size"] = 1
+    if not os.path.exists(dl["char_file"]):
+        dl["char_file"] = os.path.join(ROOT, "handwriting_line_generation_amd", "data", os.path.basename(dl["char_file"]))
+    if test:
+        dl["a_batch_size"] = val["a_batch_size"] = 1
+        print("changed a_batch_size to 1", flush=True)
+        loader, _ = getDataLoader(config, "test")
+    else:
+        _, loader = getDataLoader(config, "train")
+    if loader is None or not len(loader.dataset):
+        raise SystemExit("generate.py: the %s split of %s holds no lines" % ("test" if test else "validation", dl.get("data_dir")))
+    return loader
+
+
+def _write_frames(images, args, frame=None):
+    """images: list of NCHW [B,1,H,W] device tensors (one per frame, widths may differ) -> gen<b>_<i>.png (--shard: index b * frames + i),
+    converted to 8-bit on the GPU; `frame(i)` true: a 1-pixel black border, drawn on the host array"""
+    from handwriting_line_generation_amd import ops
+    sink = LineSink(args.savedir, "%s.png", args.shard, args.writers)
+    try:
+        for i, image in enumerate(images):
+            B, _, H, W = image.shape
+            pixels, offsets = ops.lines_to_u8(image, [W] * B)
+            host = pixels.cpu().numpy()
+            for b in range(B):
+                line = host[offsets[b]:offsets[b + 1]].reshape(H, W)
+                if frame is not None and frame(i):
+                    line = line.copy()
+                    line[0, :] = line[-1, :] = 0
+                    line[:, 0] = line[:, -1] = 0
+                sink.add(b * len(images) + i if args.shard else "gen%d_%d" % (b, i), line)
+    finally:
+        sink.close()
+    return sink.count
+
+
+def run_s(model, config, char_to_idx, run, args, gpu):
+    """the reference's `s` action (generate.py:278-305)"""
+    import torch
+    from handwriting_line_generation_amd import ops
+    from handwriting_line_generation_amd.generate import get_style, interpolate_horz
+    from handwriting_line_generation_amd.model.hw_with_style import correct_pred
+    index = int(run["batch"]) if run.get("batch") else 0
+    if index < 0:
+        raise SystemExit("generate.py: choice=s takes batch=<index from 0>, got %d" % index)
+    for i, instance in enumerate(dataset_loader(config, args.test)):      # (never empty: dataset_loader refuses a split without lines)
+        if i == index:
+            break
+    else:
+        print("the split holds %d batches: batch %d taken (as the reference takes the last)" % (i + 1, i), flush=True)
+    model.count_std = model.dup_std = 0          # reference generate.py:199-200
+    with torch.no_grad():
+        style = get_style(config, model, instance, gpu)
+        image, label = ops.h2d(instance["image"], gpu), ops.h2d(instance["label"], gpu)
+        pred = model.hwr(image, None)
+        aligned = pred if config.get("trainer", {}).get("use_hwr_pred_for_style", False) else correct_pred(pred, label)
+        images = interpolate_horz(model, style, aligned)
+        return _write_frames(images, args)
+
+
+def run_r(model, config, char_to_idx, run, args, rand, gpu):
+    """the reference's `r` action (generate.py:306-353)"""
+    import torch
+    from handwriting_line_generation_amd.generate import walk_film, walk_styles
+    num_styles, step = int(run["num_styles"]), float(run.get("step", 0.1))
+    if num_styles < 2 or not 0 < step <= 1:
+        raise SystemExit("generate.py: choice=r needs num_styles of at least 2 and a step in (0, 1]")
+    text = run.get("text", "") or PANGRAM
+    start = int(run["start"]) if run.get("start") else None
+    stride = int(run["stride"]) if run.get("stride") else None
+    model.count_std = model.dup_std = 0
+    with torch.no_grad():
+        styles = walk_styles(dataset_loader(config, args.test), model, config, num_styles, rand, gpu, start, stride)
+        images, frame_styles = walk_film(model, styles, text, char_to_idx, gpu, step)
+        n = _write_frames(images, args, frame=(lambda i: i % 5 == 0) if step == 0.2 else None)
+    for b in range(images[0].shape[0]):
+        torch.save(frame_styles, os.path.join(args.savedir, "styles%d.pth" % b))
+    return n
+
+
+def run_A(model, config, char_to_idx, run, args, gpu):
+    """the reference's `A` action (generate.py:501-527)"""
+    import torch
+    from handwriting_line_generation_amd import ops
+    from handwriting_line_generation_amd.generate import author_mean_style, generate
+    text = run.get("text", "") or PANGRAM
+    max_hits = int(run["max"]) if run.get("max") else 5
+    model.count_std = model.dup_std = 0
+    sink = LineSink(args.savedir, "%s.png", args.shard, args.writers)
+    try:
+        with torch.no_grad():
+            style = author_mean_style(dataset_loader(config, args.test), model, config, run["author"], gpu, max_hits)
+            image = generate(model, style, text, char_to_idx, gpu)
+            _, _, H, W = image.shape
+            pixels, offsets = ops.lines_to_u8(image, [W])
+            sink.add(0 if args.shard else "gen_%s" % run["author"], pixels.cpu().numpy().reshape(H, W))
+    finally:
+        sink.close()
+    return sink.count
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="MI355X-native handwriting line generation from a checkpoint")
     ap.add_argument("-c", "--checkpoint", type=str, default=None, help="checkpoint of this package or of the reference")
@@ -239,7 +352,11 @@ def main(argv=None):
     ap.add_argument("-g", "--gpu", type=int, default=0)
     ap.add_argument("-f", "--config", type=str, default=None, help="config file to use instead of the checkpoint's")
     ap.add_argument("-a", "--addtoconfig", type=str, default=None, help="k1=v1,k2=k3=v2: config[k1]=v1, config[k2][k3]=v2 (int / float coerced, empty = null)")
-    ap.add_argument("-r", "--run", type=str, default=None, help="choice=R,num=N,text=... | choice=f,path1=..,path2=..,text=..")
+    ap.add_argument("-r", "--run", type=str, default=None, help="choice=R,num=N,text=... | choice=f,path1=..,path2=..,text=.. | choice=u | choice=s[,batch=i] (the "
+                    "stretch film of one validation batch: the aligned text is re-sampled by one HIP launch for all 79 frames; with "
+                    "trainer.use_hwr_pred_for_style the recogniser's own output is stretched instead, through torch's F.interpolate, not "
+                    "the kernel) | choice=r,num_styles=K,step=0.1[,text=..][,start=i,stride=n] | choice=A,author=<id>[,text=..][,max=5]")
+    ap.add_argument("-T", "--test", action="store_true", help="choice=s|r|A: read the test split, one line per batch (default: validation)")
     ap.add_argument("-s", "--style_loc", type=str, default=None, help="style pickle (prefix) written by evaluate.dump_styles")
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--batch", type=int, default=64, help="lines rendered per batch")
@@ -253,9 +370,14 @@ def main(argv=None):
     run = parse_run(args.run)
     choice = run.get("choice", "")
     if choice not in CHOICES:
-        raise NotImplementedError("generate.py: action %r is not built; the three that exist are 'R' (random interpolated styles from a style "
-                                  "file), 'f' (interpolation between the styles of two line images) and 'u' (the pictures umap_styles.py "
-                                  "pastes into its map)" % choice)
+        raise NotImplementedError("generate.py: action %r is not built; the six that exist are 'R' (random interpolated styles from a style "
+                                  "file), 'f' (interpolation between the styles of two line images), 'u' (the pictures umap_styles.py "
+                                  "pastes into its map), 's' (stretch film of a validation batch), 'r' (walk through the styles of "
+                                  "several writers) and 'A' (a writer's mean style)" % choice)
+    if choice == "r" and not run.get("num_styles"):
+        raise SystemExit("generate.py: choice=r needs num_styles=<writers to walk through> (and takes step=0.1,text=...,start=,stride=)")
+    if choice == "A" and not run.get("author"):
+        raise SystemExit("generate.py: choice=A needs author=<writer id of the split>")
     if args.checkpoint is None:
         raise SystemExit("generate.py: must provide a checkpoint (with -c)")
     if args.savedir is None:
@@ -277,8 +399,14 @@ def main(argv=None):
         n = run_R(model, config, char_to_idx, run, args, rand, gpu)
     elif choice == "f":
         n = run_f(model, config, char_to_idx, run, args, gpu)
-    else:
+    elif choice == "u":
         n = run_u(model, config, char_to_idx, run, args, gpu)
+    elif choice == "s":
+        n = run_s(model, config, char_to_idx, run, args, gpu)
+    elif choice == "r":
+        n = run_r(model, config, char_to_idx, run, args, rand, gpu)
+    else:
+        n = run_A(model, config, char_to_idx, run, args, gpu)
     torch.cuda.synchronize()
     dt = time.time() - t0
     print("lines %d  seconds %.3f  lines/s %.1f" % (n, dt, n / dt if dt > 0 else 0.0), flush=True)

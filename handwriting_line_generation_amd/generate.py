@@ -105,6 +105,135 @@ def interpolate(model, style1, style2, text, char_to_idx, gpu, step=0.05):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
+# the reference's figure actions: `s` stretch film, `r` walk through writers' styles, `A` a writer's mean style
+# `hook`: tests set it to hook(kind, tensors) and see the device tensors behind the pictures - "stretch": aligned (the index [T,B], or the
+# recogniser's output [T,B,C]), frames (the list of one-hots the generator was given), style; "walk": styles (list of [1, style_dim]);
+# "author": styles (list of [1, style_dim]), style (their mean [1, style_dim])
+hook = None
+
+
+def stretch_scales():
+    """the 79 horizontal scale factors of the reference's stretch film (generate.py:834-851), built from the same np.arange calls so that the
+    float drift of the steps is the reference's: 12 from arange(1, 1.11, .01), 12 repeats of the last, 22 from arange(1.1, .89, -.01), 22 repeats
+    of the last, 11 from arange(.9, 1.01, .01). The repeats are the reference's two "vertical" loops: they change nothing and render the label
+    of the loop before them again, with fresh generator noise - kept, so that the film has the reference's frames."""
+    wider, narrower, back = np.arange(1, 1.11, 0.01), np.arange(1.1, 0.89, -0.01), np.arange(0.9, 1.01, 0.01)
+    scales = [float(s) for s in wider] + [float(wider[-1])] * len(np.arange(1, 1.11, 0.01))
+    scales += [float(s) for s in narrower] + [float(narrower[-1])] * len(np.arange(1.1, 0.89, -0.01))
+    return scales + [float(s) for s in back]
+
+
+def interpolate_horz(model, style, aligned):
+    """the reference's interpolate_horz (generate.py:830-852): the line(s) behind `aligned` rendered once per stretch_scales() entry, the
+    character spacing stretched and squeezed along the line -> list of 79 images NCHW [B,1,64,4 T_out]. `aligned`: the DTW-aligned class
+    indices int [T,B] on the device (correct_pred) - ONE ops.stretch_onehot launch makes all 79 interpolated one-hots, in the layout the
+    generator reads - or the recogniser's own output, float [T,B,C] (trainer.use_hwr_pred_for_style): nothing to index, the frames are
+    torch's F.interpolate on the device, as in the reference. `style`: one writer's, [1, style_dim], expanded to the batch. The generator is
+    called directly (no _clip_spaced), as the reference does."""
+    if style.numel() != style.shape[-1]:
+        raise ValueError("interpolate_horz: the style must be one writer's, [1, style_dim], got %s" % (tuple(style.shape),))
+    B = aligned.shape[1]
+    style = style.reshape(1, -1).expand(B, -1).contiguous()
+    scales = stretch_scales()
+    if aligned.dim() == 2:
+        frames = ops.stretch_onehot(aligned.to(torch.int32).contiguous(), model.num_class, scales)
+    else:
+        import torch.nn.functional as F
+        orig = aligned.permute(1, 2, 0)
+        frames, last = [], None
+        for k, s in enumerate(scales):
+            if last is None or s != scales[k - 1]:
+                last = F.interpolate(orig, scale_factor=s, mode="linear").permute(2, 0, 1).contiguous()
+            frames.append(last)
+    if hook is not None:
+        hook("stretch", {"aligned": aligned, "frames": frames, "style": style})
+    return [model.generator(frame, style) for frame in frames]
+
+
+def _writer_style(model, config, instance, gpu):
+    """model.extract_style(image, label, a_batch_size)[::a_batch_size] of one batch (generate.py:320-323, 515-518) -> [writers, style_dim];
+    the extractor's cached recogniser output and alignment are cleared around the call, and it reads the recogniser's prediction or the
+    aligned text as trainer.use_hwr_pred_for_style says (as get_style does)"""
+    image, label = instance["image"], instance["label"]
+    if gpu is not None:
+        image = image if image.is_cuda else ops.h2d(image, gpu)
+        label = label if label.is_cuda else ops.h2d(label, gpu)
+    a_batch_size = instance["a_batch_size"]
+    old = model.use_hwr_pred_for_style
+    model.use_hwr_pred_for_style = bool(config.get("trainer", {}).get("use_hwr_pred_for_style", False))
+    try:
+        model.pred = model.spaced_label = model.spaced_label_index = None
+        return model.extract_style(image, label, a_batch_size)[::a_batch_size].contiguous()
+    finally:
+        model.use_hwr_pred_for_style = old
+        model.pred = model.spaced_label = model.spaced_label_index = None
+
+
+def walk_batches(loader, num_styles, rand, start=None, stride=None):
+    """the batches the reference's `r` action takes its styles from (generate.py:314-329), as (i, instance): the first at index
+    rand.randint(0, 20) (`start` when given), then every batch with i >= index whose writer differs from the last one taken, after which
+    index += rand.randint(20, 50) (`stride` when given; the draw is not made then); stops after the batch at which num_styles are reached."""
+    index = rand.randint(0, 20) if start is None else int(start)
+    last_author, taken = None, 0
+    for i, instance in enumerate(loader):
+        author = instance["author"][0]
+        if i >= index and author != last_author:
+            yield i, instance
+            taken += 1
+            last_author = author
+            index += rand.randint(20, 50) if stride is None else int(stride)
+        if taken >= num_styles:
+            break
+
+
+def walk_styles(loader, model, config, num_styles, rand, gpu, start=None, stride=None):
+    """the styles of the reference's `r` action: one [1, style_dim] per batch walk_batches selects. Fewer than 2 is a SystemExit."""
+    seen = [0]
+
+    def counted():
+        for instance in loader:
+            seen[0] += 1
+            yield instance
+    styles = [_writer_style(model, config, instance, gpu) for _, instance in walk_batches(counted(), num_styles, rand, start, stride)]
+    if len(styles) < 2:
+        raise SystemExit("generate.py: choice=r walks between the styles of at least 2 writers, found %d in the %d batches of the split "
+                         "(start / stride reach fewer batches than it holds?)" % (len(styles), seen[0]))
+    if hook is not None:
+        hook("walk", {"styles": styles})
+    return styles
+
+
+def walk_film(model, styles, text, char_to_idx, gpu, step=0.1):
+    """the closed walk (generate.py:335-341): interpolate(styles[i], styles[i + 1]) for every neighbour pair, then from the last back to the
+    first -> (list of images, list of the host styles of every frame)"""
+    images, frame_styles = [], []
+    for k in range(len(styles)):
+        b_im, b_sty = interpolate(model, styles[k], styles[(k + 1) % len(styles)], text, char_to_idx, gpu, step)
+        images += b_im
+        frame_styles += b_sty
+    return images, frame_styles
+
+
+def author_mean_style(loader, model, config, author, gpu, max_hits=5):
+    """the style of the reference's `A` action (generate.py:511-523): the mean over the styles of the first `max_hits` batches of writer
+    `author` -> [1, style_dim]. A writer the split does not hold is a SystemExit."""
+    styles, seen = [], 0
+    for i, instance in enumerate(loader):
+        seen = i + 1
+        if str(instance["author"][0]) == str(author):
+            print("{} found on instance {}".format(author, i), flush=True)
+            styles.append(_writer_style(model, config, instance, gpu))
+            if len(styles) >= max_hits:
+                break
+    if not styles:
+        raise SystemExit("generate.py: choice=A found no line of writer %r in the %d batches of the split" % (author, seen))
+    style = torch.cat(styles, dim=0).mean(dim=0)[None, ...].contiguous()
+    if hook is not None:
+        hook("author", {"styles": styles, "style": style})
+    return style
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
 # from a checkpoint to pictures: what the reference's `generate.py -c ... -d ... -s ...` program does around the calls above
 def apply_add_to_config(config, adds):
     """the reference's `-a` rule (generate.py:116-136): every entry [k1, ..., kn, value] sets config[k1]...[kn] = value, the value coerced

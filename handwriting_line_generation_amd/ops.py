@@ -1749,6 +1749,90 @@ def nhwc_of(content_LBC):
     return None
 
 
+def stretch_frames(T, scales):
+    """host side of stretch_onehot: per scale s the (T_out, r, identity) F.interpolate(x [.., T], scale_factor=s, mode='linear') works with -
+    T_out = floor(double(T) * s), r = float32(1 / s), identity = (T_out == T: torch copies its input then, whatever s is). A scale that
+    leaves no step is a ValueError."""
+    import math
+    import numpy as np
+    frames = []
+    for s in scales:
+        s = float(s)
+        if not (s > 0.0 and math.isfinite(s)):
+            raise ValueError("stretch_onehot: scale %r is not a positive finite number" % s)
+        T_out = int(math.floor(float(T) * s))
+        if T_out < 1:
+            raise ValueError("stretch_onehot: scale %r leaves no step of a line of %d" % (s, T))
+        frames.append((T_out, np.float32(1.0 / s), T_out == T))
+    return frames
+
+
+def stretch_onehot(label_TB, ncls, scales, out=None, offsets=None):
+    """The stretch film's labels (csrc/stretch.hip): label int32 [T,B] (the aligned line, device or host) -> a list with one time-major
+    tensor [T_out,B,ncls] per scale, the one-hot of the line re-sampled along time as F.interpolate(scale_factor=s, mode='linear') does
+    on the CPU, bit for bit (stretch_frames); each carries its NHWC rows [B,1,T_out,ncls] as `_hwg_nhwc`, as onehot_both's result does.
+    One launch fills all frames; the tensors are views into two ragged fp32 buffers, every frame starting at a multiple of 4 floats.
+    The labels and the scales are validated here, before anything is uploaded or launched: a class outside [0, ncls) or a frame without
+    steps is a ValueError. `out`: (blc, lbc), two contiguous 1-D fp32 device buffers to write into, with `offsets` = (offsets into blc,
+    offsets into lbc): one multiple of 4 per frame, frames inside their buffer and apart from each other; nothing else of the buffers
+    is written."""
+    import numpy as np
+    if not torch.is_tensor(label_TB) or label_TB.dim() != 2 or label_TB.dtype != torch.int32:
+        raise L.HwgError("stretch_onehot: label must be an int32 [T,B] tensor")
+    T, B = label_TB.shape
+    ncls = int(ncls)
+    if T < 1 or B < 1 or ncls < 1:
+        raise L.HwgError("stretch_onehot: bad sizes T=%d B=%d ncls=%d" % (T, B, ncls))
+    frames = stretch_frames(T, scales)
+    F = len(frames)
+    if F < 1:
+        raise ValueError("stretch_onehot: no scales")
+    host = label_TB.cpu().numpy()
+    if ((host < 0) | (host >= ncls)).any():
+        raise ValueError("stretch_onehot: labels must lie in [0, %d), got %d .. %d" % (ncls, host.min(), host.max()))
+    sizes = np.asarray([B * f[0] * ncls for f in frames], dtype=np.int64)
+    if out is None:
+        if offsets is not None:
+            raise L.HwgError("stretch_onehot: offsets without out")
+        if not label_TB.is_cuda:
+            raise L.HwgError("stretch_onehot: a host label needs `out` to name the device")
+        off = np.zeros(F, dtype=np.int64)
+        np.cumsum((sizes[:-1] + 3) // 4 * 4, out=off[1:])
+        offs = (off, off)
+        total = int(off[-1] + sizes[-1])
+        bufs = (torch.empty((total,), dtype=torch.float32, device=label_TB.device), torch.empty((total,), dtype=torch.float32, device=label_TB.device))
+    else:
+        bufs = tuple(out)
+        if len(bufs) != 2 or offsets is None or len(offsets) != 2:
+            raise L.HwgError("stretch_onehot: out = (blc, lbc) goes with offsets = (offsets into blc, offsets into lbc)")
+        offs = tuple(np.asarray(o, dtype=np.int64).reshape(-1) for o in offsets)
+        for buf, off, name in zip(bufs, offs, ("blc", "lbc")):
+            if not torch.is_tensor(buf) or not buf.is_cuda or buf.dtype != torch.float32 or buf.dim() != 1 or not buf.is_contiguous() or buf.data_ptr() % 16:
+                raise L.HwgError("stretch_onehot: out %s must be a contiguous, 16-byte aligned 1-D fp32 device buffer" % name)
+            if off.shape[0] != F or (off % 4 != 0).any() or (off < 0).any() or (off + sizes > buf.numel()).any():
+                raise L.HwgError("stretch_onehot: %s offsets must be %d multiples of 4 with every frame inside the buffer, got %s" % (name, F, off.tolist()))
+            order = np.argsort(off, kind="stable")
+            if (off[order][1:] < (off + sizes)[order][:-1]).any():
+                raise L.HwgError("stretch_onehot: %s frames overlap: offsets %s, sizes %s" % (name, off.tolist(), sizes.tolist()))
+    dev = bufs[0].device
+    table = np.zeros(F, dtype=np.dtype([("T_out", np.int32), ("r", np.float32), ("identity", np.int32), ("reserved", np.int32),
+                                        ("off_blc", np.int64), ("off_lbc", np.int64)]))       # hwg_stretch_frame, 32 bytes
+    table["T_out"] = [f[0] for f in frames]
+    table["r"] = [f[1] for f in frames]
+    table["identity"] = [f[2] for f in frames]
+    table["off_blc"], table["off_lbc"] = offs
+    table_d = h2d(torch.from_numpy(table.view(np.int64)), dev)          # (int64 words: the records hold 8-byte fields)
+    label_d = label_TB.contiguous() if label_TB.is_cuda else h2d(label_TB.contiguous(), dev)
+    L.call("hwg_stretch_onehot", label_d, T, B, ncls, table_d, F, max(f[0] for f in frames), bufs[0], bufs[0].numel(), bufs[1],
+           bufs[1].numel(), _stream())
+    result = []
+    for k, (T_out, _, _) in enumerate(frames):
+        lbc = bufs[1][int(offs[1][k]):int(offs[1][k]) + int(sizes[k])].view(T_out, B, ncls)
+        lbc._hwg_nhwc = bufs[0][int(offs[0][k]):int(offs[0][k]) + int(sizes[k])].view(B, 1, T_out, ncls)
+        result.append(lbc)
+    return result
+
+
 def permute4(x, dims, strides):
     out = torch.empty(tuple(dims), dtype=torch.float32, device=x.device)
     L.call("hwg_permute4", x, out, dims[0], dims[1], dims[2], dims[3], strides[0], strides[1], strides[2], strides[3], _stream())

@@ -544,6 +544,32 @@ int hwg_lines_from_u8(const unsigned char* pixels, long long pixel_bytes, const 
                       const int* select, int min_select, const float* real, int Br, int Wr, int B, int H, int W, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The stretch film's labels (csrc/stretch.hip; generate.py:830-852 interpolate_horz: per frame a dense one-hot, permute(1,2,0),
+ * F.interpolate(scale_factor=s, mode='linear'), permute(2,0,1) - 79 times per film).
+ * label [T][B] int32: the aligned line (generate.py:298 correct_pred), blanks 0. frames: a device array of F records. Frame f is the
+ * one-hot of `label` re-sampled along time to T_out steps, written twice: as [B][T_out][ncls] at out_blc + off_blc (NHWC rows, what
+ * the generator reads) and as [T_out][B][ncls] at out_lbc + off_lbc (the reference's time-major tensor); offsets count floats and are
+ * multiples of 4. One launch writes every element of every frame, zeros included; nothing else of the two buffers is touched.
+ * Arithmetic (torch's CPU kernel, bit for bit): identity != 0 (the host sets it where T_out == T: torch copies then, whatever s is)
+ * gives the plain one-hot; otherwise src = fmaf(r, t + 0.5f, -0.5f) with ONE rounding, src = max(src, 0), i0 = min((int)src, T - 1),
+ * i1 = min(i0 + 1, T - 1), w1 = src - i0, w0 = 1 - w1, out[c] = w0 * [label[i0] == c] + w1 * [label[i1] == c]. The host computes
+ * T_out = floor((double)T * s) and r = (float)(1.0 / s).
+ * Checked here before the launch: no NULL, T, B, ncls, max_T_out >= 1, 1 <= F <= 65535, T < 2^23, B * max_T_out * ncls below 2^31,
+ * buffers 16-byte aligned. The table is the caller's to check (ops.stretch_onehot validates it on the host before the upload, and the
+ * labels: a class outside [0, ncls) is an error there); a record that is bad all the same - T_out outside [1, max_T_out], a misaligned
+ * block or one that ends behind blc_elems / lbc_elems floats - writes nothing, and a label outside [0, ncls) matches no class.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct hwg_stretch_frame {
+  int T_out;                  /* steps of this frame                                   */
+  float r;                    /* (float)(1.0 / s)                                      */
+  int identity;               /* T_out == T: the plain one-hot                         */
+  int reserved;
+  long long off_blc, off_lbc; /* first float of the frame in out_blc / out_lbc         */
+} hwg_stretch_frame;
+int hwg_stretch_onehot(const int* label, int T, int B, int ncls, const hwg_stretch_frame* frames, int F, int max_T_out, float* out_blc,
+                       long long blc_elems, float* out_lbc, long long lbc_elems, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Sample sheets of GAN training (trainer/hw_with_style_trainer.py:992-1010: torchvision's save_image(1 - images, nrow, normalize=True),
  * there on the host after downloading the fp32 batch). x: images [B][1][H][W] fp32, n = B * H * W.
  * v = 1 - x; lo / hi = min / max of the finite v over the whole tensor; d = (float)max((double)hi - (double)lo, 1e-5);

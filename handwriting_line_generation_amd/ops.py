@@ -7,6 +7,7 @@ released checkpoints load; the kernels read/write those layouts directly through
 Nothing in this module computes on the CPU or through ATen math kernels: every op is a call into
 libhwg_hip.so on torch's current stream. torch is used for memory, autograd bookkeeping and views.
 """
+import collections
 import ctypes
 import math
 import os
@@ -687,29 +688,51 @@ def _prof_tag(shape):
 _RUN_SCOPE = [None]     # scope of the conv op currently being executed (forward: SCOPE, backward: the scope saved at forward time)
 
 
-_conv_plans = {}    # geometry -> (descriptor, workspace bytes): descriptors are built (and the library's schedule queried) once per geometry
+_conv_plans = {}    # geometry -> (descriptor, workspace bytes, descriptor address): built (and the library's schedule queried) once per geometry
+_CONV_ENTRY = ("hwg_conv_fwd", "hwg_wino_conv_fwd", "hwg_wino_s2_conv")      # entry families: direct, Winograd F(2x2,3x3), two-tap Winograd F(3x3,2x2)
+_CONV_WORKSPACE = ("hwg_conv_fwd_workspace", "hwg_wino_conv_workspace", "hwg_wino_s2_workspace")
 
 
 def static_host_ptrs():
     """addresses of the host-side descriptors that live as long as the plan caches (what a recorded call list may hold as literal host
-    pointers - replay.py rejects every other host address: a temporary's address would dangle on replay)"""
+    pointers - replay.py rejects every other host address: a temporary's address would dangle on replay); lowerings hold _conv_plans entries"""
     out = {int(p[2]) for p in _conv_plans.values()}
-    out.update(int(p[0].ptr) for p in _wgrad_plans.values())
+    out.update(int(p.d.ptr) for p in _wgrad_plans.values())
     return out
 
 
-def _run_conv(x, wp, bias, N, H, W, C, K, R, S, stride, pad, dil, P, Q, transposed, wino=False):
-    y = torch.empty((N, P, Q, K), dtype=torch.float32, device=x.device)
+# One library product a layer's forward or data gradient is lowered to (integers and a descriptor only, never a tensor): entry family (index
+# into _CONV_ENTRY), its _conv_plans entry, the channel count the contraction side is zero-padded to (or None), _pack's arguments (A, B, R, S,
+# sa, sb, flip, Bpad, wino), the result's shape and, or None, the launch that follows as (entry, result shape, integers): hwg_col2im_taps
+# folding a tap matrix back into the image, hwg_pad2d_fwd restoring rows the filter never met
+_Product = collections.namedtuple("_Product", "wino plan cpad pack oshape post")
+
+
+def _product(pack, cpad, N, H, W, C, K, R, S, stride, pad, dil, P, Q, transposed, post=None):
+    wino = pack[8]
     key = (N, H, W, C, K, R, S, stride, pad, dil, P, Q, transposed, wino)
     plan = _conv_plans.get(key)
     if plan is None:
         d = _desc(N, H, W, C, K, R, S, stride, pad, dil, P, Q, transposed)
-        plan = _conv_plans[key] = (d, L.query(("hwg_conv_fwd_workspace", "hwg_wino_conv_workspace", "hwg_wino_s2_workspace")[int(wino)], d.ptr), d.ptr)
-    d, need, dptr = plan
+        plan = _conv_plans[key] = (d, L.query(_CONV_WORKSPACE[wino], d.ptr), d.ptr)
+    return _Product(wino, plan, cpad, pack, (N, P, Q, K), post)
+
+
+def _run_conv(prod, x, weight, bias):
+    """execute a lowered product: pad, pack, launch, post step"""
+    if prod.cpad is not None:
+        x = _pad_channels(x, prod.cpad)
+    wp = _pack(weight, *prod.pack)
+    y = torch.empty(prod.oshape, dtype=torch.float32, device=x.device)
+    d, need, dptr = prod.plan
     if PROF_SHAPES is not None:
-        _prof_tag((N, H, W, C, K, R, S, stride, pad, dil, transposed, _RUN_SCOPE[0]))
+        _prof_tag((d.N, d.H, d.W, d.C, d.K, d.R, d.S, (d.stride_h, d.stride_w), (d.pad_h, d.pad_w), (d.dil_h, d.dil_w), d.transposed, _RUN_SCOPE[0]))
     ws = workspace(need, x.device) if need else None
-    L.call(("hwg_conv_fwd", "hwg_wino_conv_fwd", "hwg_wino_s2_conv")[int(wino)], dptr, x, wp, bias, y, 0, ws, need, _stream())
+    L.call(_CONV_ENTRY[prod.wino], dptr, x, wp, bias, y, 0, ws, need, _stream())
+    if prod.post is not None:
+        entry, oshape, ints = prod.post
+        t, y = y, torch.empty(oshape, dtype=torch.float32, device=x.device)
+        L.call(entry, t, y, *ints, _stream())
     return y
 
 
@@ -730,7 +753,7 @@ def tuning_reload():
     global WINOGRAD, TUNE_EPOCH
     TUNE_EPOCH += 1
     WINOGRAD = bool(int(os.environ.get("HWG_WINO", "1") or 1))
-    _wino_choice.clear(); _wino_wgrad_choice.clear(); _conv_plans.clear(); _wgrad_plans.clear(); _wgrad_sets_ok.clear(); _wgrad_sets_ws.clear()
+    _wino_choice.clear(); _wino_wgrad_choice.clear(); _conv_plans.clear(); _wgrad_plans.clear(); _fwd_lowerings.clear(); _dgrad_lowerings.clear()
     L.call("hwg_tuning_reload")
 
 
@@ -832,35 +855,193 @@ def _taps(weight):
     raise L.HwgError("conv weight must have 2, 3 or 4 dimensions")
 
 
+_fwd_lowerings = {}      # (N, H, W, C, K, R, S, stride, padding, dilation, transposed, output_padding) -> (_Product, effective stride, P, Q)
+_dgrad_lowerings = {}    # (dy's N, H, W, C, K, R, S, effective stride, padding, dilation, transposed, P, Q) -> _Product
+
+
+def _lower_forward(N, H, W, C, K, R, S, stride, padding, dilation, transposed, output_padding):
+    """the library product a layer's forward becomes -> (_Product, the stride backward sees, P, Q)"""
+    sh, sw = stride; ph, pw = padding; dh, dw = dilation
+    if not transposed:
+        P = (H + 2 * ph - dh * (R - 1) - 1) // sh + 1
+        Q = (W + 2 * pw - dw * (S - 1) - 1) // sw + 1
+        Cp = _cpad(C, K)
+        if Cp == C and _wino_s2_ok(N, H, W, C, K, R, S, stride, padding, dilation, P, Q, 0):
+            return _product((K, C, 4, 4, C * 16, 16, 0, None, 2), None, N, H, W, C, K, 4, 4, (2, 2), (0, 0), (1, 1), P, Q, 0), stride, P, Q
+        wino = int(_wino_ok(N, H, W, Cp, K, R, S, stride, padding, dilation, P, Q))
+        return _product((K, C, R, S, C * R * S, R * S, 0, Cp, wino), Cp if Cp != C else None, N, H, W, Cp, K, R, S, stride, padding, dilation, P, Q, 0), stride, P, Q
+    oph, opw = output_padding
+    if H == 1 and sh == 1 and ph == 0 and dh == 1 and dw == 1 and R > 1 and oph == 0:
+        # ONE input row (the generator's 1-D -> 2-D lift, ConvTranspose (4,3)): output row p takes tap row r = p and nothing else, so
+        # the layer is its own stride-(R, sw) twin. Run as that fractionally strided layer every output row is a parity class with
+        # its 1 x S taps; as a stride-1 layer it is a correlation over R x S taps of which R - 1 rows only ever meet padding
+        # (4 x the multiplies: 62 -> 25 us at 8 lines, 325 -> 100 us at a generation batch of 64). Backward follows the returned stride.
+        sh = R
+        stride = (R, sw)
+    P = (H - 1) * sh - 2 * ph + dh * (R - 1) + 1 + oph
+    Q = (W - 1) * sw - 2 * pw + dw * (S - 1) + 1 + opw
+    Cp = _cpad(C, K, fractional=(sh != 1 or sw != 1))
+    cpad = Cp if Cp != C else None
+    if sh == 1 and sw == 1:
+        # stride-1 transposed conv == correlation with mirrored taps and padding dil*(R-1)-pad
+        pad = (dh * (R - 1) - ph, dw * (S - 1) - pw)
+        wino = int(_wino_ok(N, H, W, Cp, K, R, S, (1, 1), pad, dilation, P, Q))
+        return _product((K, C, R, S, R * S, K * R * S, 1, Cp, wino), cpad, N, H, W, Cp, K, R, S, (1, 1), pad, dilation, P, Q, 0), stride, P, Q
+    assert dh == 1 and dw == 1, "strided conv_transpose needs dilation 1"
+    return _product((K, C, R, S, R * S, K * R * S, 0, Cp, 0), cpad, N, H, W, Cp, K, R, S, stride, padding, (1, 1), P, Q, 1), stride, P, Q
+
+
+def _lower_dgrad(N, H, W, C, K, R, S, stride, padding, dilation, transposed, P, Q):
+    """the library product a layer's data gradient becomes: a contraction over K (dy's channels) producing C channels; N is dy's batch"""
+    sh, sw = stride; ph, pw = padding; dh, dw = dilation
+    Kp = _cpad(K, C, fractional=(not transposed and (sh != 1 or sw != 1)))
+    kpad = Kp if Kp != K else None
+    if transposed:
+        # gradient of a transposed conv is an ordinary (strided) correlation of dy
+        wino = int(_wino_ok(N, P, Q, Kp, C, R, S, stride, padding, dilation, H, W))
+        return _product((C, K, R, S, K * R * S, R * S, 0, Kp, wino), kpad, N, P, Q, Kp, C, R, S, stride, padding, dilation, H, W, 0)
+    if C == 1 and sh == 1 and sw == 1 and K % 16 == 0 and 1 < R * S <= 64:
+        # single-channel input (first layers): dx has one channel, so instead of a matrix-vector kernel the tap matrix
+        # t[pixel][tap] = dy x W^T is formed by a 1x1 convolution on the matrix cores and folded back by col2im (379 -> ~40 us for
+        # the discriminator's 7x7 in_conv at 8 x 64 x 512). The packed image is [1][taps][K]: element (tap, k) = w[k][0][tap]; K % 16 == 0
+        # needs no padding
+        return _product((R * S, K, 1, 1, 1, R * S, 0, None, 0), None, N, P, Q, K, R * S, 1, 1, (1, 1), (0, 0), (1, 1), P, Q, 0,
+                        post=("hwg_col2im_taps", (N, H, W, 1), (N, H, W, P, Q, R, S, ph, pw, dh, dw)))
+    if sh == 1 and sw == 1 and P == 1 and ph == 0 and dh == 1 and dw == 1 and R > 1 and Kp % 16 == 0 and C > 2:
+        # ONE row of output gradients (the recogniser's last 3x3 layer: three rows in, one out): input row r receives tap row r
+        # and nothing else - a fractionally strided layer with stride (R, 1) whose row classes have 1 x S taps each. As a stride-1
+        # correlation with padding R - 1 two thirds of the multiplies meet padding (97 -> ~55 us at 8 x 1 x 126 x 512 -> 512).
+        return _product((C, K, R, S, R * S, C * R * S, 0, Kp, 0), kpad, N, P, Q, Kp, C, R, S, (R, 1), (0, pw), (1, 1), H, W, 1)
+    if sh == 1 and sw == 1:
+        pad = (dh * (R - 1) - ph, dw * (S - 1) - pw)
+        wino = int(_wino_ok(N, P, Q, Kp, C, R, S, (1, 1), pad, dilation, H, W))
+        return _product((C, K, R, S, R * S, C * R * S, 1, Kp, wino), kpad, N, P, Q, Kp, C, R, S, (1, 1), pad, dilation, H, W, 0)
+    if Kp == K and _wino_s2_ok(N, P, Q, K, C, R, S, stride, padding, dilation, H, W, 1):
+        return _product((K, C, 4, 4, C * 16, 16, 1, None, 2), None, N, P, Q, K, C, 4, 4, (2, 2), (0, 0), (1, 1), H, W, 1)
+    assert dh == 1 and dw == 1, "strided conv backward needs dilation 1"
+    pack = (C, K, R, S, R * S, C * R * S, 0, Kp, 0)
+    if P == 1 and ph == 0 and R > sh:
+        # one output row (so R <= H < R + sh): the vertical stride never moves - stride R gives every input row its own class of 1 x S taps
+        # where stride sh pairs each class with R / sh tap rows of which all but one meet nothing; the style extractor's last 4x4
+        # stride-(2,1) layer.
+        # (H > R: rows R.. of the input never met the filter - the style extractor's last block sees 5 rows and uses 4. They
+        # get zeros; the R live rows run as the stride-R twin instead of sh-strided classes whose second block row is dead:
+        # 4x1x254x256 -> 4x5x257x256: 81 -> ~50 us)
+        dead = ("hwg_pad2d_fwd", (N, H, W, C), (N, R, W, C, 0, H - R, 0, 0, 0, 0.0)) if H > R else None
+        return _product(pack, kpad, N, P, Q, Kp, C, R, S, (R, sw), padding, (1, 1), R, W, 1, post=dead)
+    return _product(pack, kpad, N, P, Q, Kp, C, R, S, stride, padding, (1, 1), H, W, 1)
+
+
 _wgrad_plans = {}
-_wgrad_sets_ok = {}
-_wgrad_sets_ws = {}
+
+
+class _WgradPlan:
+    """A layer's weight gradient as the library runs it (integers and a descriptor only, never a tensor): descriptor; engine 0 = Winograd
+    F(3x3,2x2), 1 = MFMA kernel on channel-padded copies (Kq, Cq: the counts rounded up to multiples of 4, also in the descriptor), 2 = MFMA /
+    direct kernel on the tensors as they are; need = workspace bytes of one launch; anchor_dy: dy is the kernel's anchor operand and x the
+    gathered one (a transposed layer swaps them); S, sa, sb: tap columns and the gradient's channel strides in the parameter's layout;
+    fuse_bias_ok: the bias gradient (column sums of dy) can ride along; tag: the launches' profile label, without the scope"""
+    __slots__ = ("d", "engine", "need", "Kq", "Cq", "tiny_end", "tap_gemm", "anchor_dy", "S", "sa", "sb", "fuse_bias_ok", "tag", "_sets_ok", "_sets_ws")
+
+    def sets_ok(self):
+        """the S weight gradients of several gradient sets can run as ONE launch (asked once, when a grouped pass first meets the layer)"""
+        if self._sets_ok is None:
+            self._sets_ok = self.engine != 1 and not (self.engine == 0 and not self.anchor_dy) and not self.tiny_end and (
+                self.engine == 0 or bool(L.query("hwg_conv_wgrad_sets_supported", self.d.ptr)))
+        return self._sets_ok
+
+    def sets_ws(self, S):
+        if S not in self._sets_ws:
+            self._sets_ws[S] = L.query("hwg_wino_wgrad_sets_workspace" if self.engine == 0 else "hwg_conv_wgrad_sets_workspace", self.d.ptr, S)
+        return self._sets_ws[S]
 
 
 def _make_wgrad_plan(N, H, W, C, K, R, S, sh, sw, ph, pw, dh, dw, P, Q, transposed):
-    """(descriptor, engine, workspace bytes, Kq, Cq, tiny_end, tap_gemm) of a weight gradient; engine 0 = Winograd F(3x3,2x2),
-    1 = MFMA kernel on channel-padded copies, 2 = MFMA / direct kernel on the tensors as they are"""
-    if not transposed:
-        d = _desc(N, H, W, C, K, R, S, (sh, sw), (ph, pw), (dh, dw), P, Q)
-    else:
-        d = _desc(N, P, Q, K, C, R, S, (sh, sw), (ph, pw), (dh, dw), H, W)
-    Kq, Cq = (d.K + 3) // 4 * 4, (d.C + 3) // 4 * 4
+    p = _WgradPlan()
+    d = _desc(N, P, Q, K, C, R, S, (sh, sw), (ph, pw), (dh, dw), H, W) if transposed else _desc(N, H, W, C, K, R, S, (sh, sw), (ph, pw), (dh, dw), P, Q)
+    p.d, p.Kq, p.Cq = d, (d.K + 3) // 4 * 4, (d.C + 3) // 4 * 4
     # single-channel ends (C == 1 first layers, K <= 2 heads) have a direct kernel; on large images the MFMA kernel on a
     # 4-channel zero-padded copy is faster (measured 164 vs 390 us for the 7x7 first layer of D), so only small ones stay direct
     # (the direct kernel runs a K<=2 head as ONE workgroup: 166 us for the discriminator's 256->1 3x3 head at 304 pixels, so heads
     # with a wide gathered side go through the padded MFMA path as well; only narrow-and-small cases stay direct)
-    tiny_end = ((d.C == 1 and d.K % 4 == 0 and d.K > 2) or (d.K <= 2 and d.C % 4 == 0 and d.C < 16)) and d.N * d.P * d.Q < 8192
+    p.tiny_end = ((d.C == 1 and d.K % 4 == 0 and d.K > 2) or (d.K <= 2 and d.C % 4 == 0 and d.C < 16)) and d.N * d.P * d.Q < 8192
     # single gathered channel (first layers): the library runs the taps as the GEMM's N dimension, no padding needed
-    tap_gemm = d.C == 1 and d.K > 2 and d.K % 4 == 0 and R * S <= 64
-    if _wino_wgrad_ok(d):
-        return d, 0, L.query("hwg_wino_wgrad_workspace", d.ptr), Kq, Cq, tiny_end, tap_gemm
-    if (Kq != d.K or Cq != d.C) and not tiny_end and not tap_gemm:
-        d.K, d.C = Kq, Cq
-        return d, 1, L.query("hwg_conv_wgrad_workspace", d.ptr), Kq, Cq, tiny_end, tap_gemm
-    return d, 2, L.query("hwg_conv_wgrad_workspace", d.ptr), Kq, Cq, tiny_end, tap_gemm
+    p.tap_gemm = d.C == 1 and d.K > 2 and d.K % 4 == 0 and R * S <= 64
+    # engine 1: channel counts that are not multiples of 4 (RIMES: 78 classes -> 206/334-channel inputs, 78 outputs): the kernel runs on
+    # zero-padded copies and the valid block of its result is kept
+    p.engine = 0 if _wino_wgrad_ok(d) else 1 if (p.Kq != d.K or p.Cq != d.C) and not p.tiny_end and not p.tap_gemm else 2
+    # The bias gradient rides along only when dy is the kernel's anchor operand (not transposed) and, on the MFMA engine, the MFMA path runs.
+    # Engine 1 never fuses it, never defers its sum and never leaves the main stream.
+    p.fuse_bias_ok = not transposed and (p.engine == 0 or (p.engine == 2 and not p.tiny_end and d.K > 2 and (d.C > 2 or p.tap_gemm)))
+    if p.engine == 1:
+        d.K, d.C = p.Kq, p.Cq
+    p.need = L.query("hwg_wino_wgrad_workspace" if p.engine == 0 else "hwg_conv_wgrad_workspace", d.ptr)
+    p.anchor_dy, p.S, p.sa, p.sb = not transposed, S, (K if transposed else C) * R * S, R * S
+    p.tag = (d.N, d.H, d.W, d.C, d.K, R, S, (sh, sw), (ph, pw), (dh, dw), "wgrad")
+    p._sets_ok, p._sets_ws = None, {}
+    return p
 
 
-ONEROW_TWIN_DEAD_ROWS = bool(int(os.environ.get("HWG_ONEROW_DEAD_ROWS", "1") or 0))     # 0: inputs with dead rows (H > R, one output row) keep the sh-strided classes (A/B)
+def _wgrad_begin(ctx, dy):
+    """what every weight-gradient path starts with -> (the layer's plan, anchor operand, gathered operand); descriptor, engine choice and
+    workspace size are fixed per geometry: built once (the library's cost models run there)"""
+    x, weight = ctx.saved_tensors
+    _RUN_SCOPE[0] = ctx.scope
+    stride, padding, dilation, transposed, P, Q = ctx.geom
+    pkey = tuple(x.shape) + (dy.shape[3],) + _taps(weight) + stride + padding + dilation + (P, Q, transposed)
+    plan = _wgrad_plans.get(pkey)
+    if plan is None:
+        plan = _wgrad_plans[pkey] = _make_wgrad_plan(*pkey)
+    if PROF_SHAPES is not None:
+        _prof_tag(plan.tag + (ctx.scope,))
+    return (plan, dy, x) if plan.anchor_dy else (plan, x, dy)
+
+
+def _fused_bias_dest(ctx, plan, device):
+    """where the bias gradient that rides along with a weight-gradient launch goes -> (dbias, bacc, db): the buffer the kernel writes, whether
+    it accumulates there, and what goes back to autograd (None: accumulated in place). (None, 0, None): nothing rides along - no bias
+    gradient is wanted, or the launch cannot carry it and the caller sums dy's columns itself"""
+    if not (ctx.has_bias and ctx.needs_input_grad[2] and plan.fuse_bias_ok):
+        return None, 0, None
+    bref = ctx.param_refs[1]
+    if _direct(bref):
+        return _grad_buffer(bref), 1, None
+    db = torch.empty((plan.d.K,), dtype=torch.float32, device=device)
+    return db, 0, db
+
+
+def _bias_colsum(dy, bref):
+    """the bias gradient as a launch of its own -> the gradient, or None where it was accumulated into the parameter's buffer"""
+    cols = dy.view(-1, dy.shape[3])
+    if not _direct(bref):
+        return colsum(cols)
+    colsum(cols, out=_grad_buffer(bref), accumulate=True)
+
+
+def _wgrad_route(plan, nbytes, device, operands, direct, bias_ok, ask_arena, eager_ws):
+    """Where one weight-gradient launch of engine 0 or 2 goes -> (stream, workspace); queues the deferred sum and forks the side stream.
+    bias_ok: no bias gradient rides along, or it accumulates in place (a returned one is read right after the launch).
+    ask_arena: the partial images go to a slice of the deferred-sum arena; with bias_ok their sum is only queued (hwg_wgrad_defer_next), else
+    the slice serves as plain workspace. A full arena means workspace and an immediate sum. With SIDE_WGRAD the MFMA engine's launch for a
+    parameter's own buffer goes to the side stream (dy and x are complete on the main stream when it forks; operands held until the join), the
+    Winograd engine's never. eager_ws: the single-gradient path asks for the shared scratch buffer before it is known that the launch leaves
+    the main stream (the order of scratch requests is part of recorded launch lists)."""
+    st = _stream()
+    arena = ws = _defer_workspace(nbytes, device) if ask_arena else None
+    side = SIDE_WGRAD and direct and bias_ok and plan.engine == 2
+    if ws is None and (eager_ws or not side):
+        ws = workspace(nbytes, device)
+    if side:
+        s2, st2, skey = _side_stream(device)
+        L.call("hwg_stream_fork", st, st2)
+        if arena is None:
+            ws = _side_workspace(nbytes, device, s2)
+        st = st2
+        _side_hold.append(operands)
+        _side_dirty.add(skey)
+    if arena is not None and bias_ok:
+        L.call("hwg_wgrad_defer_next")
+    return st, ws
 
 
 class _Conv2d(Function):
@@ -874,45 +1055,18 @@ class _Conv2d(Function):
         # Linear [O,I] and Conv1d [O,I,S] parameters are used as they are (same memory as [O,I,1,S]); a .view() of the parameter would be a
         # non-leaf tensor, lose the packed-weight cache and the direct gradient accumulation and cost three extra ATen ops per backward
         R, S = _taps(weight)
-        sh, sw = stride; ph, pw = padding; dh, dw = dilation
         if not transposed:
             K = weight.shape[0]
             assert weight.shape[1] == C, "conv: weight expects %d input channels, got %d" % (weight.shape[1], C)
-            P = (H + 2 * ph - dh * (R - 1) - 1) // sh + 1
-            Q = (W + 2 * pw - dw * (S - 1) - 1) // sw + 1
-            Cp = _cpad(C, K)
-            xin = _pad_channels(x, Cp) if Cp != C else x
-            if Cp == C and _wino_s2_ok(N, H, W, C, K, R, S, (sh, sw), (ph, pw), (dh, dw), P, Q, 0):
-                wp = _pack(weight, K, C, 4, 4, C * 16, 16, flip=0, wino=2)
-                y = _run_conv(x, wp, bias, N, H, W, C, K, 4, 4, (2, 2), (0, 0), (1, 1), P, Q, 0, 2)
-            else:
-                wino = _wino_ok(N, H, W, Cp, K, R, S, (sh, sw), (ph, pw), (dh, dw), P, Q)
-                wp = _pack(weight, K, C, R, S, C * R * S, R * S, flip=0, Bpad=Cp, wino=wino)
-                y = _run_conv(xin, wp, bias, N, H, W, Cp, K, R, S, (sh, sw), (ph, pw), (dh, dw), P, Q, 0, wino)
         else:
             K = weight.shape[1]
             assert weight.shape[0] == C, "conv_transpose: weight expects %d input channels, got %d" % (weight.shape[0], C)
-            oph, opw = output_padding
-            if H == 1 and sh == 1 and ph == 0 and dh == 1 and dw == 1 and R > 1 and oph == 0:
-                # ONE input row (the generator's 1-D -> 2-D lift, ConvTranspose (4,3)): output row p takes tap row r = p and nothing else, so
-                # the layer is its own stride-(R, sw) twin. Run as that fractionally strided layer every output row is a parity class with
-                # its 1 x S taps; as a stride-1 layer it is a correlation over R x S taps of which R - 1 rows only ever meet padding
-                # (4 x the multiplies: 62 -> 25 us at 8 lines, 325 -> 100 us at a generation batch of 64). Backward follows ctx.geom.
-                sh = R
-                stride = (R, sw)
-            P = (H - 1) * sh - 2 * ph + dh * (R - 1) + 1 + oph
-            Q = (W - 1) * sw - 2 * pw + dw * (S - 1) + 1 + opw
-            Cp = _cpad(C, K, fractional=(sh != 1 or sw != 1))
-            xin = _pad_channels(x, Cp) if Cp != C else x
-            if sh == 1 and sw == 1:
-                # stride-1 transposed conv == correlation with mirrored taps and padding dil*(R-1)-pad
-                wino = _wino_ok(N, H, W, Cp, K, R, S, (1, 1), (dh * (R - 1) - ph, dw * (S - 1) - pw), (dh, dw), P, Q)
-                wp = _pack(weight, K, C, R, S, R * S, K * R * S, flip=1, Bpad=Cp, wino=wino)
-                y = _run_conv(xin, wp, bias, N, H, W, Cp, K, R, S, (1, 1), (dh * (R - 1) - ph, dw * (S - 1) - pw), (dh, dw), P, Q, 0, wino)
-            else:
-                assert dh == 1 and dw == 1, "strided conv_transpose needs dilation 1"
-                wp = _pack(weight, K, C, R, S, R * S, K * R * S, flip=0, Bpad=Cp)
-                y = _run_conv(xin, wp, bias, N, H, W, Cp, K, R, S, (sh, sw), (ph, pw), (1, 1), P, Q, 1)
+        key = (N, H, W, C, K, R, S, stride, padding, dilation, transposed, output_padding)
+        low = _fwd_lowerings.get(key)
+        if low is None:
+            low = _fwd_lowerings[key] = _lower_forward(*key)
+        prod, stride, P, Q = low
+        y = _run_conv(prod, x, weight, bias)
         ctx.save_for_backward(x, weight)
         ctx.has_bias = bias is not None
         ctx.param_refs = (weight, bias)
@@ -948,6 +1102,56 @@ class _Conv2d(Function):
         return (dx, None if dws[0] is None else SetGrad(S, parts=dws), None if dbs[0] is None else SetGrad(S, parts=dbs), None, None, None, None, None)
 
     @staticmethod
+    def _dgrad(ctx, dy):
+        x, weight = ctx.saved_tensors
+        _RUN_SCOPE[0] = ctx.scope
+        # (dy's batch may be a multiple of x's: several gradient sets through the same layer)
+        key = (dy.shape[0],) + tuple(x.shape[1:]) + (dy.shape[3],) + _taps(weight) + ctx.geom
+        prod = _dgrad_lowerings.get(key)
+        if prod is None:
+            prod = _dgrad_lowerings[key] = _lower_dgrad(*key)
+        return _run_conv(prod, dy, weight, None)
+
+    @staticmethod
+    def _wgrad(ctx, dy):
+        """-> (dw, db) as tensors, or None where the kernel accumulated straight into the parameter's gradient buffer"""
+        dw_ = db = dbias = None
+        wref, bref = ctx.param_refs
+        if ctx.needs_input_grad[1]:
+            plan, u, v = _wgrad_begin(ctx, dy)
+            direct = _direct(wref)
+            dw_ = _grad_buffer(wref) if direct else torch.empty_like(ctx.saved_tensors[1])
+            acc = 1 if direct else 0
+            if plan.engine == 1:
+                # the kernel runs on zero-padded copies (the plan's descriptor carries the padded counts)
+                Kq, Cq, S, RS = plan.Kq, plan.Cq, plan.S, plan.sb
+                dK, dC = u.shape[3], v.shape[3]
+                up = _pad_channels(u, Kq) if Kq != dK else u
+                vp = _pad_channels(v, Cq) if Cq != dC else v
+                tmp = torch.empty((Kq, Cq, RS // S, S), dtype=torch.float32, device=dy.device)
+                ws = workspace(plan.need, dy.device)
+                L.call("hwg_conv_wgrad", plan.d.ptr, up, vp, tmp, Cq * RS, RS, S, 1, 0, None, 0, ws, ws.numel(), _stream())
+                # the valid block of the padded result, added to (or copied into) the gradient through the C-ABI: row k of `tmp` holds Cq*R*S floats
+                # of which the first dC*R*S belong to real channels (a torch-side add_ here was invisible to a recorded call list: every RIMES
+                # geometry of the recogniser failed its replay self-check)
+                L.call("hwg_copy_channels", tmp, Cq * RS, 0, dw_, dC * RS, 0, dC * RS, dK, 1, 0, acc, _stream())
+            else:
+                dbias, bacc, db = _fused_bias_dest(ctx, plan, dy.device)
+                # the sum of the partial images may wait for the flush behind the backward pass where nothing reads the gradient earlier: a
+                # parameter's buffer, or the dW_sn of a spectral-norm layer whose own backward is queued for the same flush (_SpectralScale).
+                # The arena is asked before the bias is looked at.
+                late = direct or getattr(wref, "_hwg_sn_defer", False)
+                st, ws = _wgrad_route(plan, plan.need, dy.device, (u, v), direct, dbias is None or bacc == 1,
+                                      ask_arena=bool(DEFER_REDUCE and late and plan.need), eager_ws=True)
+                L.call("hwg_wino_wgrad" if plan.engine == 0 else "hwg_conv_wgrad", plan.d.ptr, u, v, dw_, plan.sa, plan.sb, plan.S, 1, acc, dbias, bacc,
+                       ws, ws.numel(), st)
+            if direct:
+                dw_ = None
+        if ctx.has_bias and ctx.needs_input_grad[2] and dbias is None:
+            db = _bias_colsum(dy, bref)
+        return dw_, db
+
+    @staticmethod
     def _wgrad_sets(ctx, dy, S, targets):
         """the S weight gradients of this layer as ONE launch (hwg_conv_wgrad_sets / hwg_wino_wgrad_sets: the layer input is shared, every set
         has its own pixel ranges, partial images and destination buffer). -> (per-set dw list, per-set db list) with None where the kernels
@@ -956,255 +1160,40 @@ class _Conv2d(Function):
         import numpy as np
         if not ctx.needs_input_grad[1]:
             return None
-        x, weight = ctx.saved_tensors
-        _RUN_SCOPE[0] = ctx.scope
-        stride, padding, dilation, transposed, P, Q = ctx.geom
-        N, H, W, C = x.shape
-        R, S_ = _taps(weight)
-        sh, sw = stride; ph, pw = padding; dh, dw = dilation
-        K = dy.shape[3]
-        pkey = (N, H, W, C, K, R, S_, sh, sw, ph, pw, dh, dw, P, Q, transposed)
-        plan = _wgrad_plans.get(pkey)
-        if plan is None:
-            plan = _wgrad_plans[pkey] = _make_wgrad_plan(*pkey)
-        d, engine, need, Kq, Cq, tiny_end, tap_gemm = plan
-        ok = _wgrad_sets_ok.get(pkey)
-        if ok is None:
-            ok = _wgrad_sets_ok[pkey] = engine != 1 and not (engine == 0 and transposed) and not tiny_end and (
-                engine == 0 or bool(L.query("hwg_conv_wgrad_sets_supported", d.ptr)))
-        if not ok:
+        plan, u, v = _wgrad_begin(ctx, dy)
+        if not plan.sets_ok():
             return None
+        weight = ctx.saved_tensors[1]
         wref, bref = ctx.param_refs
         direct = _direct(wref)
-        want_bias = ctx.has_bias and ctx.needs_input_grad[2]
-        fuse_bias = want_bias and not transposed and (engine == 0 or (d.K > 2 and (d.C > 2 or tap_gemm)))
-        bdirect = _direct(bref) if want_bias else False
-        dws, dbs, dws_out, dbs_out = [], [], [], []
+        dws, dbs, dws_out, dbs_out, bacc = [], [], [], [], 0
         for s_ in range(S):
             GRAD_SET = targets[s_]
             dws.append(_grad_buffer(wref) if direct else torch.empty_like(weight))
             dws_out.append(None if direct else dws[-1])
-            if fuse_bias:
-                dbs.append(_grad_buffer(bref) if bdirect else torch.empty((K,), dtype=torch.float32, device=x.device))
-                dbs_out.append(None if bdirect else dbs[-1])
+            dbias, bacc, db = _fused_bias_dest(ctx, plan, dy.device)
+            if dbias is not None:
+                dbs.append(dbias); dbs_out.append(db)
         wptr = np.array([t.data_ptr() for t in dws], dtype=np.int64)
-        bptr = np.array([t.data_ptr() for t in dbs], dtype=np.int64) if fuse_bias else None
-        if not transposed:
-            u, v, set_on_v = dy, x, 0
-            sa, sb = C * R * S_, R * S_
+        btab = np.array([t.data_ptr() for t in dbs], dtype=np.int64)
+        bptr = btab.ctypes.data if dbs else None
+        total = plan.sets_ws(S)
+        bias_ok = not dbs or bacc == 1
+        # (here the bias is looked at first: the arena is only asked where the sum can wait, for a parameter's own buffer)
+        st, ws = _wgrad_route(plan, total, dy.device, (u, v), direct, bias_ok, ask_arena=bool(DEFER_REDUCE and direct and bias_ok and total), eager_ws=False)
+        if plan.engine == 0:
+            L.call("hwg_wino_wgrad_sets", plan.d.ptr, u, v, S, wptr.ctypes.data, plan.sa, plan.sb, plan.S, 1, 1 if direct else 0, bptr, bacc, ws, ws.numel(), st)
         else:
-            u, v, set_on_v = x, dy, 1
-            sa, sb = K * R * S_, R * S_
-        acc = 1 if direct else 0
-        bacc = 1 if (fuse_bias and bdirect) else 0
-        tkey = (pkey, S)
-        total = _wgrad_sets_ws.get(tkey)
-        if total is None:
-            total = _wgrad_sets_ws[tkey] = L.query("hwg_wino_wgrad_sets_workspace" if engine == 0 else "hwg_conv_wgrad_sets_workspace", d.ptr, S)
-        can_defer = DEFER_REDUCE and direct and (not fuse_bias or bdirect) and total
-        ws = _defer_workspace(total, x.device) if can_defer else None
-        defer = ws is not None
-        st = _stream()
-        if PROF_SHAPES is not None:
-            _prof_tag((d.N, d.H, d.W, d.C, d.K, R, S_, (sh, sw), (ph, pw), (dh, dw), "wgrad", ctx.scope))
-        side = SIDE_WGRAD and direct and engine == 2 and (not fuse_bias or bdirect)
-        if side:
-            s2, raw2, skey = _side_stream(x.device)
-            L.call("hwg_stream_fork", st, raw2)
-            if ws is None:
-                ws = _side_workspace(total, x.device, s2)
-            st = raw2
-            _side_hold.append((u, v))
-            _side_dirty.add(skey)
-        elif ws is None:
-            ws = workspace(total, x.device)
-        if defer:
-            L.call("hwg_wgrad_defer_next")
-        if engine == 0:
-            L.call("hwg_wino_wgrad_sets", d.ptr, u, v, S, wptr.ctypes.data, sa, sb, S_, 1, acc, bptr.ctypes.data if fuse_bias else None, bacc,
+            L.call("hwg_conv_wgrad_sets", plan.d.ptr, u, v, S, 0 if plan.anchor_dy else 1, wptr.ctypes.data, plan.sa, plan.sb, plan.S, 1, 1 if direct else 0, bptr, bacc,
                    ws, ws.numel(), st)
-        else:
-            L.call("hwg_conv_wgrad_sets", d.ptr, u, v, S, set_on_v, wptr.ctypes.data, sa, sb, S_, 1, acc, bptr.ctypes.data if fuse_bias else None, bacc,
-                   ws, ws.numel(), st)
-        if want_bias and not fuse_bias:
+        if ctx.has_bias and ctx.needs_input_grad[2] and not dbs:
             n = dy.shape[0] // S
             for s_ in range(S):
                 GRAD_SET = targets[s_]
-                part = dy[s_ * n:(s_ + 1) * n]
-                if bdirect:
-                    colsum(part.view(-1, K), out=_grad_buffer(bref), accumulate=True)
-                    dbs_out.append(None)
-                else:
-                    dbs_out.append(colsum(part.view(-1, K)))
+                dbs_out.append(_bias_colsum(dy[s_ * n:(s_ + 1) * n], bref))
         if not dbs_out:
             dbs_out = [None] * S
         return dws_out, dbs_out
-
-    @staticmethod
-    def _dgrad(ctx, dy):
-        x, weight = ctx.saved_tensors
-        _RUN_SCOPE[0] = ctx.scope
-        stride, padding, dilation, transposed, P, Q = ctx.geom
-        N, H, W, C = x.shape
-        N = dy.shape[0]              # (may be a multiple of x's batch: several gradient sets through the same layer)
-        R, S = _taps(weight)
-        sh, sw = stride; ph, pw = padding; dh, dw = dilation
-        K = dy.shape[3]
-        dx = None
-        st = _stream()
-        if True:
-            # data gradient: contraction over K (dy's channels) producing C channels
-            Kp = _cpad(K, C, fractional=(not transposed and (sh != 1 or sw != 1)))
-            dyin = _pad_channels(dy, Kp) if Kp != K else dy
-            if not transposed and C == 1 and sh == 1 and sw == 1 and K % 16 == 0 and 1 < R * S <= 64:
-                # single-channel input (first layers): dx has one channel, so instead of a matrix-vector kernel the tap matrix
-                # t[pixel][tap] = dy x W^T is formed by a 1x1 convolution on the matrix cores and folded back by col2im (379 -> ~40 us for
-                # the discriminator's 7x7 in_conv at 8 x 64 x 512)
-                wt = _pack(weight, R * S, K, 1, 1, 1, R * S, flip=0)           # [1][taps][K]: element (tap, k) = w[k][0][tap]
-                t = _run_conv(dy, wt, None, N, P, Q, K, R * S, 1, 1, (1, 1), (0, 0), (1, 1), P, Q, 0)
-                dx = torch.empty((N, H, W, 1), dtype=torch.float32, device=x.device)
-                L.call("hwg_col2im_taps", t, dx, N, H, W, P, Q, R, S, ph, pw, dh, dw, st)
-            elif not transposed:
-                if sh == 1 and sw == 1 and P == 1 and ph == 0 and dh == 1 and dw == 1 and R > 1 and Kp % 16 == 0 and C > 2:
-                    # ONE row of output gradients (the recogniser's last 3x3 layer: three rows in, one out): input row r receives tap row r
-                    # and nothing else - a fractionally strided layer with stride (R, 1) whose row classes have 1 x S taps each. As a stride-1
-                    # correlation with padding R - 1 two thirds of the multiplies meet padding (97 -> ~55 us at 8 x 1 x 126 x 512 -> 512).
-                    wp = _pack(weight, C, K, R, S, R * S, C * R * S, flip=0, Bpad=Kp)
-                    dx = _run_conv(dyin, wp, None, N, P, Q, Kp, C, R, S, (R, 1), (0, pw), (1, 1), H, W, 1)
-                elif sh == 1 and sw == 1:
-                    wino = _wino_ok(N, P, Q, Kp, C, R, S, (1, 1), (dh * (R - 1) - ph, dw * (S - 1) - pw), (dh, dw), H, W)
-                    wp = _pack(weight, C, K, R, S, R * S, C * R * S, flip=1, Bpad=Kp, wino=wino)
-                    dx = _run_conv(dyin, wp, None, N, P, Q, Kp, C, R, S, (1, 1), (dh * (R - 1) - ph, dw * (S - 1) - pw), (dh, dw), H, W, 0, wino)
-                elif Kp == K and _wino_s2_ok(N, P, Q, K, C, R, S, (sh, sw), (ph, pw), (dh, dw), H, W, 1):
-                    wp = _pack(weight, K, C, 4, 4, C * 16, 16, flip=1, wino=2)
-                    dx = _run_conv(dy, wp, None, N, P, Q, K, C, 4, 4, (2, 2), (0, 0), (1, 1), H, W, 1, 2)
-                else:
-                    assert dh == 1 and dw == 1, "strided conv backward needs dilation 1"
-                    wp = _pack(weight, C, K, R, S, R * S, C * R * S, flip=0, Bpad=Kp)
-                    # (one output row, H == R: the vertical stride never moves - stride R gives every input row its own class of 1 x S taps
-                    # where stride sh pairs each class with R / sh tap rows of which all but one meet nothing; the style extractor's last
-                    # 4x4 stride-(2,1) layer)
-                    if P == 1 and ph == 0 and R > sh and (H == R or (H > R and ONEROW_TWIN_DEAD_ROWS)):
-                        # (H > R: rows R.. of the input never met the filter - the style extractor's last block sees 5 rows and uses 4. They
-                        # get zeros; the R live rows run as the stride-R twin instead of sh-strided classes whose second block row is dead:
-                        # 4x1x254x256 -> 4x5x257x256: 81 -> ~50 us)
-                        dx = _run_conv(dyin, wp, None, N, P, Q, Kp, C, R, S, (R, sw), (ph, pw), (1, 1), R, W, 1)
-                        if H > R:
-                            full = torch.empty((N, H, W, C), dtype=torch.float32, device=dx.device)
-                            L.call("hwg_pad2d_fwd", dx, full, N, R, W, C, 0, H - R, 0, 0, 0, 0.0, st)
-                            dx = full
-                    else:
-                        dx = _run_conv(dyin, wp, None, N, P, Q, Kp, C, R, S, (sh, sw), (ph, pw), (1, 1), H, W, 1)
-            else:
-                # gradient of a transposed conv is an ordinary (strided) correlation of dy
-                wino = _wino_ok(N, P, Q, Kp, C, R, S, (sh, sw), (ph, pw), (dh, dw), H, W)
-                wp = _pack(weight, C, K, R, S, K * R * S, R * S, flip=0, Bpad=Kp, wino=wino)
-                dx = _run_conv(dyin, wp, None, N, P, Q, Kp, C, R, S, (sh, sw), (ph, pw), (dh, dw), H, W, 0, wino)
-        return dx
-
-    @staticmethod
-    def _wgrad(ctx, dy):
-        """-> (dw, db) as tensors, or None where the kernel accumulated straight into the parameter's gradient buffer"""
-        x, weight = ctx.saved_tensors
-        _RUN_SCOPE[0] = ctx.scope
-        stride, padding, dilation, transposed, P, Q = ctx.geom
-        N, H, W, C = x.shape
-        R, S = _taps(weight)
-        sh, sw = stride; ph, pw = padding; dh, dw = dilation
-        K = dy.shape[3]
-        dw_ = db = None
-        bias_done = False
-        st = _stream()
-        wref, bref = ctx.param_refs
-        if ctx.needs_input_grad[1]:
-            direct = _direct(wref)
-            dw_ = _grad_buffer(wref) if direct else torch.empty_like(weight)
-            # descriptor, engine choice and workspace size are fixed per geometry: built once (the library's cost models run there)
-            pkey = (N, H, W, C, K, R, S, sh, sw, ph, pw, dh, dw, P, Q, transposed)
-            plan = _wgrad_plans.get(pkey)
-            if plan is None:
-                plan = _wgrad_plans[pkey] = _make_wgrad_plan(*pkey)
-            d, engine, need, Kq, Cq, tiny_end, tap_gemm = plan
-            if not transposed:
-                u, v = dy, x
-                sa, sb = C * R * S, R * S
-            else:
-                u, v = x, dy
-                sa, sb = K * R * S, R * S
-            # the sum of the partial images may wait for the flush behind the backward pass where nothing reads the gradient earlier: a
-            # parameter's buffer, or the dW_sn of a spectral-norm layer whose own backward is queued for the same flush (_SpectralScale)
-            late = direct or getattr(wref, "_hwg_sn_defer", False)
-            dws = _defer_workspace(need, x.device) if (DEFER_REDUCE and late and engine != 1 and need) else None
-            if engine == 0:
-                ws = dws if dws is not None else workspace(need, x.device)
-                if PROF_SHAPES is not None:
-                    _prof_tag((d.N, d.H, d.W, d.C, d.K, R, S, (sh, sw), (ph, pw), (dh, dw), "wgrad", ctx.scope))
-                dbias = bacc = None
-                if ctx.has_bias and ctx.needs_input_grad[2] and not transposed:     # dy is the kernel's anchor operand: its column sums ride along
-                    bdirect = _direct(bref)
-                    dbias = _grad_buffer(bref) if bdirect else torch.empty((K,), dtype=torch.float32, device=x.device)
-                    bacc = 1 if bdirect else 0
-                    bias_done = True
-                    if not bdirect:
-                        db = dbias
-                if dws is not None and (dbias is None or bacc):
-                    L.call("hwg_wgrad_defer_next")
-                L.call("hwg_wino_wgrad", d.ptr, u, v, dw_, sa, sb, S, 1, 1 if direct else 0, dbias, bacc or 0, ws, ws.numel(), st)
-                if direct:
-                    dw_ = None
-            elif engine == 1:
-                # channel counts that are not multiples of 4 (RIMES: 78 classes -> 206/334-channel inputs, 78 outputs): run the kernel
-                # on zero-padded copies and keep the valid block of the result (the plan's descriptor carries the padded counts)
-                dK, dC = (K, C) if not transposed else (C, K)
-                up = _pad_channels(u, Kq) if Kq != dK else u
-                vp = _pad_channels(v, Cq) if Cq != dC else v
-                tmp = torch.empty((Kq, Cq, R, S), dtype=torch.float32, device=x.device)
-                ws = workspace(need, x.device)
-                if PROF_SHAPES is not None:
-                    _prof_tag((d.N, d.H, d.W, d.C, d.K, R, S, (sh, sw), (ph, pw), (dh, dw), "wgrad", ctx.scope))
-                L.call("hwg_conv_wgrad", d.ptr, up, vp, tmp, Cq * R * S, R * S, S, 1, 0, None, 0, ws, ws.numel(), st)
-                # the valid block of the padded result, added to (or copied into) the gradient through the C-ABI: row k of `tmp` holds Cq*R*S floats
-                # of which the first dC*R*S belong to real channels (a torch-side add_ here was invisible to a recorded call list: every RIMES
-                # geometry of the recogniser failed its replay self-check)
-                L.call("hwg_copy_channels", tmp, Cq * R * S, 0, dw_, dC * R * S, 0, dC * R * S, dK, 1, 0, 1 if direct else 0, st)
-                if direct:
-                    dw_ = None
-            else:
-                ws = dws if dws is not None else workspace(need, x.device)
-                if PROF_SHAPES is not None:
-                    _prof_tag((d.N, d.H, d.W, d.C, d.K, R, S, (sh, sw), (ph, pw), (dh, dw), "wgrad", ctx.scope))
-                # the bias gradient (column sums of dy) rides along when dy is the kernel's anchor operand and the MFMA path runs
-                fuse_bias = (ctx.has_bias and ctx.needs_input_grad[2] and not transposed and not tiny_end and d.K > 2 and (d.C > 2 or tap_gemm))
-                dbias = bacc = None
-                if fuse_bias:
-                    bdirect = _direct(bref)
-                    dbias = _grad_buffer(bref) if bdirect else torch.empty((K,), dtype=torch.float32, device=x.device)
-                    bacc = 1 if bdirect else 0
-                    bias_done = True
-                    if not bdirect:
-                        db = dbias
-                defer = dws is not None and (dbias is None or bacc)
-                if SIDE_WGRAD and direct and (dbias is None or bacc):
-                    s2, raw2, skey = _side_stream(x.device)
-                    L.call("hwg_stream_fork", st, raw2)      # dy (and x) are complete on the main stream at this point
-                    ws2 = dws if defer else _side_workspace(need, x.device, s2)
-                    if defer:
-                        L.call("hwg_wgrad_defer_next")
-                    L.call("hwg_conv_wgrad", d.ptr, u, v, dw_, sa, sb, S, 1, 1, dbias, bacc or 0, ws2, ws2.numel(), raw2)
-                    _side_hold.append((u, v))
-                    _side_dirty.add(skey)
-                else:
-                    if defer:
-                        L.call("hwg_wgrad_defer_next")
-                    L.call("hwg_conv_wgrad", d.ptr, u, v, dw_, sa, sb, S, 1, 1 if direct else 0, dbias, bacc or 0, ws, ws.numel(), st)
-                if direct:
-                    dw_ = None
-        if ctx.has_bias and ctx.needs_input_grad[2] and not bias_done:
-            if _direct(bref):
-                colsum(dy.view(-1, K), out=_grad_buffer(bref), accumulate=True)
-            else:
-                db = colsum(dy.view(-1, K))
-        return dw_, db
 
 
 def conv2d(x, weight, bias=None, stride=1, padding=0, dilation=1):

@@ -44,9 +44,6 @@ def hip(tag):
     worst = sorted(errs.items(), key=lambda kv: -kv[1])[:4]
     print("%-40s pooled %.3e  worst %s" % (tag, pooled, ["%s %.2e" % (k[-32:], v) for k, v in worst]), flush=True)
 hip("as shipped")
-ops.ONEROW_TWIN_DEAD_ROWS = False
-hip("one-row twin only for H == R")
-ops.ONEROW_TWIN_DEAD_ROWS = True
 orig_mp = ops.max_pool2d
 ops.max_pool2d = lambda x, kernel, stride=None, padding=0, relu=False: (ops.bias_act(orig_mp(x, kernel, stride, padding), None, None, ops.ACT_RELU) if relu else orig_mp(x, kernel, stride, padding))
 hip("ReLU as a pass of its own after the pools")

@@ -43,6 +43,6 @@ for it in range(N + 1):
         wsum = list(widths); widths[0] = widths[1] = 0
         if TRIM:
             torch.cuda.empty_cache()
-        caches = {k: len(getattr(ops, k)) for k in ("_conv_plans", "_wgrad_plans", "_set_views", "_ws_cache", "_wgrad_sets_ws") if hasattr(ops, k)}
+        caches = {k: len(getattr(ops, k)) for k in ("_conv_plans", "_wgrad_plans", "_set_views", "_ws_cache", "_fwd_lowerings", "_dgrad_lowerings") if hasattr(ops, k)}
         print("step %5d  %6.1f steps/s  host blocked %5.2f ms/step  mean generated T %6.1f  allocated %8.1f MB  reserved %8.1f MB  peak %8.1f MB  caches %s" % (it, (700 if it else 1) / dt, blk / (700 if it else 1) * 1e3, wsum[0] / max(wsum[1], 1), torch.cuda.memory_allocated() / 1e6, torch.cuda.memory_reserved() / 1e6,
                                                                                       torch.cuda.max_memory_allocated() / 1e6, caches), flush=True)

@@ -362,6 +362,7 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=64, help="lines rendered per batch")
     ap.add_argument("--shard", type=int, default=0, help="write lines_%%05d.npz arrays of this many lines instead of PNGs")
     ap.add_argument("--writers", type=int, default=8, help="encoder threads (at most %d)" % MAX_WRITERS)
+    ap.add_argument("--swa", action="store_true", help="generate with the averaged weights (the checkpoint's swa_state_dict)")
     args = ap.parse_args(argv)
 
     if args.run is None:
@@ -391,7 +392,8 @@ def main(argv=None):
     rand = seed_everything(args.seed)
     torch.cuda.set_device(args.gpu)
     gpu = torch.device("cuda", args.gpu)
-    model, config, char_to_idx = load_for_generation(args.checkpoint, args.config, args.gpu, add_to_config=parse_addtoconfig(args.addtoconfig))
+    model, config, char_to_idx = load_for_generation(args.checkpoint, args.config, args.gpu, add_to_config=parse_addtoconfig(args.addtoconfig),
+                                                     averaged=args.swa)
     os.makedirs(args.savedir, exist_ok=True)
 
     t0 = time.time()

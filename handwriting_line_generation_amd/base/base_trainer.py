@@ -68,6 +68,38 @@ def lr_schedule(kind, tr, iterations):
     raise NotImplementedError("learning schedule %r" % (kind,))
 
 
+def weight_averaging_config(config):
+    """The reference's weight-averaging keys of config["trainer"] (base/base_trainer.py:180-186) -> None (off) or
+    {"start", "c_iters", "decay"}: `swa` / `weight_averaging` turns it on, `swa_start` / `weight_averaging_start` is the first averaged
+    iteration, `swa_c_iters` / `weight_averaging_c_iters` the interval; a missing one is the reference's KeyError. `weight_averaging_decay`
+    (NOT a key of the reference) turns the equal-weight mean into an exponential one, see weight_averaging_alpha."""
+    tr = config["trainer"]
+    if not (tr["swa"] if "swa" in tr else tr.get("weight_averaging", False)):
+        return None
+    if config.get("optimizer_type") == "none":
+        raise ValueError("trainer.swa / trainer.weight_averaging needs a training run: optimizer_type is \"none\"")
+    start = tr["swa_start"] if "swa_start" in tr else tr["weight_averaging_start"]
+    c_iters = tr["swa_c_iters"] if "swa_c_iters" in tr else tr["weight_averaging_c_iters"]
+    if int(c_iters) < 1:
+        raise ValueError("trainer.swa_c_iters must be at least 1 (got %r)" % (c_iters,))
+    decay = tr.get("weight_averaging_decay")
+    if decay is not None and not (0.0 < float(decay) < 1.0):
+        raise ValueError("trainer.weight_averaging_decay must lie in (0, 1) (got %r)" % (decay,))
+    return {"start": int(start), "c_iters": int(c_iters), "decay": None if decay is None else float(decay)}
+
+
+def weight_averaging_alpha(iteration, start, c_iters, decay=None):
+    """Weight of the live parameters in the averaging step after `iteration`, or None when that iteration is not averaged. Steps fall on
+    start, start + c_iters, ...; the n-th of them (n = 0, 1, ...) mixes avg * (1 - alpha) + p * alpha with alpha = 1 / (n + 1): the equal-weight
+    mean of the n + 1 snapshots (SWA). n = 0 is alpha = 1, a copy. With `decay`, every step after the first uses alpha = 1 - decay (EMA)."""
+    if iteration < start or (iteration - start) % c_iters != 0:
+        return None
+    n = (iteration - start) // c_iters
+    if n == 0:
+        return 1.0
+    return 1.0 - decay if decay is not None else 1.0 / (n + 1)
+
+
 class BaseTrainer:
     def __init__(self, model, loss, metrics, resume, config, train_logger=None):
         self.config = config
@@ -147,9 +179,13 @@ class BaseTrainer:
         self.rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
         if self.rank == 0:
             _atomic_write(os.path.join(self.checkpoint_dir, "config.json"), lambda f: f.write(json.dumps(config, indent=4, sort_keys=False).encode()))
-        self.swa = False
-        if tr.get("swa") or tr.get("weight_averaging"):
-            raise NotImplementedError("weight averaging is not used by any shipped config")
+        # weight averaging (SWA / EMA): the reference keeps a second model (:180-186); here the mean lives in one flat buffer of the parameter
+        # table (FlatParams.avg). swa_origin: the iteration of the average's first snapshot (swa_start, unless a resumed run had to begin anew)
+        wa = weight_averaging_config(config)
+        self.swa = wa is not None
+        if self.swa:
+            self.swa_start, self.swa_c_iters, self.swa_decay = wa["start"], wa["c_iters"], wa["decay"]
+            self.swa_origin = self.swa_start
         self._stop = False
         if resume:
             self._resume_checkpoint(resume)
@@ -189,6 +225,8 @@ class BaseTrainer:
                 self.optimizer.param_groups[0]["lr"] = self.scheduled_lr(self.iteration)
             result = self._train_iteration(self.iteration)
             result["sec_per_iter"] = timeit.default_timer() - t0
+            if self.swa:
+                self._average_weights(self.iteration)
             for k, v in result.items():
                 if isinstance(v, (int, float)):
                     sum_log[k] = sum_log.get(k, 0.0) + v
@@ -199,7 +237,10 @@ class BaseTrainer:
                 if self.train_logger is not None:
                     self.train_logger.add_entry(log)
             if self.val_step > 0 and self.iteration % self.val_step == 0 and getattr(self, "valid", False):
-                val = self._valid_epoch()
+                if self._swa_running():
+                    val = self._valid_epoch_both()
+                else:
+                    val = self._valid_epoch()
                 self.logger.info("validation: %s", val)
             if self.iteration % self.save_step == 0:
                 self._save_checkpoint(self.iteration, {})
@@ -213,6 +254,59 @@ class BaseTrainer:
 
     def _minor_log(self, log):
         self.logger.info("Train " + ",\t".join("%s: %s" % kv for kv in log.items()))
+
+    # -- weight averaging -------------------------------------------------------------------------------------------------------------
+    def _average_weights(self, iteration):
+        """the averaging step after `iteration` (reference :233-237, which writes self.iterations - the run's length - where its comment and
+        the SWA code it cites mean self.iteration: there the weight would be one constant for the whole run; here it is the running mean's).
+        The step number is a function of the iteration, so a resumed run needs no counter."""
+        alpha = weight_averaging_alpha(iteration, self.swa_origin, self.swa_c_iters, self.swa_decay)
+        if alpha is not None:
+            # data parallel: nothing to communicate - every rank holds identical weights and runs the same deterministic element-wise kernel
+            self.flat.average_into(alpha)
+
+    def _swa_running(self):
+        return self.swa and self.flat.avg is not None
+
+    def _valid_epoch_both(self):
+        """validation with the live weights, then (reference :287-297) with the averaged ones, logged as "swa_" + key. The second pass runs
+        between two in-place exchanges of weights and average and replays the random draws of the first (same noise for both models); the
+        generators are left where the first pass left them, so a run with averaging trains exactly like one without."""
+        before = self._rng_snapshot()
+        val = self._valid_epoch()
+        after = self._rng_snapshot()
+        self._rng_restore(before)
+        self.flat.exchange_average()
+        try:
+            swa_val = self._valid_epoch()
+        finally:
+            self.flat.exchange_average()
+            self._rng_restore(after)
+        log = {"iteration": self.iteration, **val, **{"swa_" + k: v for k, v in swa_val.items()}}
+        self.logger.info("validation (averaged weights): %s", swa_val)
+        if self.train_logger is not None:
+            self.train_logger.add_entry(log)
+        return val
+
+    @staticmethod
+    def _rng_snapshot():
+        import random
+
+        import numpy as np
+        from .. import rng
+        dev = rng.device_rng() if rng.mode() == "device" else None
+        return (torch.get_rng_state(), np.random.get_state(), random.getstate(), None if dev is None else (dev, dev.offset, dev.text_offset))
+
+    @staticmethod
+    def _rng_restore(snap):
+        import random
+
+        import numpy as np
+        torch.set_rng_state(snap[0])
+        np.random.set_state(snap[1])
+        random.setstate(snap[2])
+        if snap[3] is not None:
+            dev, dev.offset, dev.text_offset = snap[3]
 
     def save(self):
         self._save_checkpoint(getattr(self, "iteration", 0), {})
@@ -237,6 +331,11 @@ class BaseTrainer:
                 # the reference's _resume_checkpoint reads this key (:456) although its own save omits it (the discriminator's Adam
                 # moments restart from zero there); writing it keeps the file loadable by both
                 state["optimizer_discriminator"] = self.optimizer_discriminator.state_dict()
+            if self._swa_running():
+                # the reference's key and layout (:362-366): a whole state dict whose parameter entries are the averaged ones
+                state["swa_state_dict"] = self.flat.averaged_state_dict(self.model)
+                if self.swa_origin != self.swa_start:
+                    state["swa_origin"] = self.swa_origin
             from .. import rng
             state["rng"] = rng.get_state()
             latest = os.path.join(self.checkpoint_dir, "checkpoint-latest.pth")
@@ -262,6 +361,14 @@ class BaseTrainer:
             self.optimizer.load_state_dict(ckpt["optimizer"])
         if self.optimizer_discriminator is not None and ckpt.get("optimizer_discriminator") is not None:
             self.optimizer_discriminator.load_state_dict(ckpt["optimizer_discriminator"])
+        if self.swa:
+            if ckpt.get("swa_state_dict") is not None:
+                self.flat.load_average(ckpt["swa_state_dict"], self.model)
+                self.swa_origin = int(ckpt.get("swa_origin", self.swa_start))
+            elif self.start_iteration > self.swa_start:
+                # averaging turned on for a run whose checkpoint has no average: a fresh one begins (with a copy) at the schedule's next step
+                steps = -(-(self.start_iteration - self.swa_start) // self.swa_c_iters)
+                self.swa_origin = self.swa_start + steps * self.swa_c_iters
         if ckpt.get("rng") is not None:
             from .. import rng
             rng.set_state(ckpt["rng"], rank=self.rank)

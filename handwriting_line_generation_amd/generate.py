@@ -259,17 +259,22 @@ def apply_add_to_config(config, adds):
     return config
 
 
-def load_for_generation(checkpoint_path, config_path=None, gpu=0, add_to_config=None, checkpoint=None):
+def load_for_generation(checkpoint_path, config_path=None, gpu=0, add_to_config=None, checkpoint=None, averaged=False):
     """-> (model, config, char_to_idx) for a checkpoint of this package or of the reference (generate.py:88-106, 187-209): the model alone, in
     eval mode on `gpu` - no trainer, no optimizer, no data loader. `style_from_normal*` weights are dropped and `pretrained*` entries of the
-    config cleared as the reference does; `checkpoint`: the file's contents where the caller has read it already; `add_to_config` entries (apply_add_to_config) are applied before the model is built; a `data_loader.char_file` that does not exist falls back to the packaged file of that name."""
+    config cleared as the reference does; `checkpoint`: the file's contents where the caller has read it already; `add_to_config` entries (apply_add_to_config) are applied before the model is built; a `data_loader.char_file` that does not exist falls back to the packaged file of that name.
+    `averaged`: load the averaged weights that a run with trainer.swa / trainer.weight_averaging wrote (`swa_state_dict`, the reference's key)
+    instead of the live ones; a checkpoint without them is a KeyError naming the key."""
     import json
     import os
     from . import model as models
     from .logger import load_checkpoint
     if checkpoint is None:
         checkpoint = load_checkpoint(checkpoint_path)
-    state = {k: v for k, v in checkpoint["state_dict"].items() if "style_from_normal" not in k}
+    if averaged and checkpoint.get("swa_state_dict") is None:
+        raise KeyError("averaged weights asked for, but the checkpoint %s has no 'swa_state_dict' (it was not written by a run with "
+                       "trainer.swa / trainer.weight_averaging, or averaging had not started yet)" % (checkpoint_path,))
+    state = {k: v for k, v in checkpoint["swa_state_dict" if averaged else "state_dict"].items() if "style_from_normal" not in k}
     if config_path is None:
         config = checkpoint["config"]
     else:

@@ -19,6 +19,9 @@ def set_mode(mode, seed=0):
     assert mode in ("device", "host")
     _state["mode"] = mode
     _state["rng"] = ops.DeviceRNG(seed) if mode == "device" else None
+    # the stream is keyed by `seed` now: a base seed left by an earlier seed_process() no longer describes it (get_state() would record it, and
+    # a resume would derive another stream from it than the one the checkpointed run drew from); seed_process / set_state put theirs back
+    _state["base_seed"] = None
 
 
 def mode():

@@ -241,6 +241,64 @@ class FlatParams:
                self._st())
         return self._flag
 
+    # -- weight averaging (SWA / EMA; reference base/base_trainer.py:233-237, 481-484) -----------------------------------
+    # The reference keeps a second model; here the running mean of EVERY parameter (frozen and ungrouped ones too, as its moving_average
+    # walks parameters()) is one flat fp32 buffer laid out like flat_grad, updated and exchanged with the live weights by one launch each.
+    avg = None
+
+    def _avg_buffer(self):
+        if self.avg is None:
+            self.avg = torch.zeros(self.total, dtype=torch.float32, device=self.device)
+            self._d_offsets = torch.from_numpy(self.offsets).to(self.device)
+        return self.avg
+
+    def average_into(self, alpha):
+        """avg = avg * (1 - alpha) + p * alpha over every parameter, rounded as torch rounds `a *= (1.0 - alpha); a += p * alpha` (both
+        scalars to fp32, a product and a sum per element): alpha = 1 copies the weights into the zero buffer"""
+        avg = self._avg_buffer()
+        ops.join_side_stream()
+        L.call("hwg_weight_average", self.d_param_ptrs, self.d_chunk_tensor, self.d_chunk_off, self.d_numel, self._d_offsets, self.nchunks, avg,
+               1.0 - float(alpha), float(alpha), self._st())
+
+    def exchange_average(self):
+        """live weights <-> averaged weights, in place: every device pointer stays what it is. Everything derived from weight VALUES is
+        invalidated the way an optimizer step does it - the kernel writes behind torch's version counters, so the packed-weight cache
+        epoch of every group is bumped and its cached images are re-packed. Two calls restore every bit."""
+        if self.avg is None:
+            raise RuntimeError("exchange_average before the first average_into: there is no averaged model yet")
+        ops.join_side_stream()
+        L.call("hwg_weight_exchange", self.d_param_ptrs, self.d_chunk_tensor, self.d_chunk_off, self.d_numel, self._d_offsets, self.nchunks, self.avg,
+               self._st())
+        for name in self.group_range:
+            ops.bump_weight_epoch((id(self), name))
+            ops.repack_group((id(self), name))
+
+    def averaged_state_dict(self, model):
+        """model.state_dict() (CPU tensors) with every parameter entry replaced by its slice of avg - the reference's `swa_state_dict`.
+        Buffers (batch-norm running statistics, spectral-norm u) are the live model's: there is only one set."""
+        if self.avg is None:
+            raise RuntimeError("averaged_state_dict before the first average_into: there is no averaged model yet")
+        avg = self.avg.cpu()
+        sd = {k: v.detach().cpu() for k, v in model.state_dict().items()}
+        for name, p in model.named_parameters(remove_duplicate=False):      # (a module registered under two names has two sets of keys)
+            if name in sd:
+                k = self.pos[self._index_of(p)]
+                sd[name] = avg[int(self.offsets[k]): int(self.offsets[k] + self.numel[k])].view(p.shape).clone()
+        return sd
+
+    def load_average(self, state_dict, model):
+        """the inverse of averaged_state_dict: fill avg from the parameter entries of a `swa_state_dict` (buffer entries are ignored)"""
+        avg = self._avg_buffer()
+        for name, p in model.named_parameters(remove_duplicate=False):
+            k = self.pos[self._index_of(p)]
+            avg[int(self.offsets[k]): int(self.offsets[k] + self.numel[k])].copy_(state_dict[name].reshape(-1))     # (a missing entry is a KeyError)
+
+    def _index_of(self, p):
+        ids = getattr(self, "_ids", None)
+        if ids is None:
+            ids = self._ids = {id(q): i for i, q in enumerate(self.params)}
+        return ids[id(p)]
+
 
 # data-parallel traffic counters (bench.py reports them per step so that a first multi-GPU run is self-diagnosing)
 COMM = {"collectives": 0, "bytes": 0}

@@ -476,6 +476,16 @@ int hwg_mt_adam(const void* ptrs_p, const void* ptrs_g, const void* ptrs_m, cons
 int hwg_mt_clip_adam(const void* ptrs_p, const void* ptrs_g, const void* ptrs_m, const void* ptrs_v, const float* step_size,
                      const float* bc2_sqrt, float beta1, float beta2, float eps, float clip, int* flag, const void* numel,
                      const void* chunk_tensor, const void* chunk_off, int nchunks, int chunk, void* stream);
+/* Weight averaging (SWA / EMA) over the same tables. avg is one fp32 buffer laid out like the flat gradient buffer: tensor t at float
+ * offsets[t] (int64 table, multiples of 4), the padding between segments is never touched. A chunk-table entry ends where the tensor's next
+ * entry begins, so no chunk size is passed.
+ * hwg_weight_average: avg_t[j] = fadd_rn(fmul_rn(avg_t[j], one_minus_alpha), fmul_rn(p_t[j], alpha)) - two roundings and no FMA, bit for bit
+ * torch's `a *= (1 - alpha); a += p * alpha` on fp32 tensors; the parameters are only read.
+ * hwg_weight_exchange: p_t[j] <-> avg_t[j] in place; two calls restore every bit. */
+int hwg_weight_average(const void* param_ptrs, const void* chunk_tensor, const void* chunk_off, const void* numel, const void* offsets,
+                       int nchunks, float* avg, float one_minus_alpha, float alpha, void* stream);
+int hwg_weight_exchange(const void* param_ptrs, const void* chunk_tensor, const void* chunk_off, const void* numel, const void* offsets,
+                        int nchunks, float* avg, void* stream);
 int hwg_randn(float* out, long long n, unsigned long long seed, unsigned long long offset, void* stream);
 int hwg_dropmask(float* out, long long n, float p, unsigned long long seed, unsigned long long offset, void* stream);
 /* the Dropout2d masks of one network pass in ONE launch (model/discriminator_ap.py:84-131 has up to six, model/autoencoder.py:341-410 four):

@@ -51,6 +51,7 @@ def parse_args(argv=None):
     ap.add_argument("-e", "--eval", default=None, type=str,
                     help='what to evaluate, a list: "pred" = the recogniser\'s reading, "recon" = reconstruction, "gen" = image generated '
                          'from interpolated styles, "style", "author" (default: [recon,pred] with a generator, else [pred])')
+    ap.add_argument("--swa", default=False, action="store_true", help="evaluate the averaged weights (the checkpoint's swa_state_dict)")
     args = ap.parse_args(argv)
     if args.checkpoint is None and args.config is None:
         raise SystemExit("new_eval.py: must provide checkpoint (with -c)")
@@ -176,13 +177,24 @@ class _Lookahead:
             p[1](*p[0].finish())
 
 
+def load_model(args, checkpoint, config):
+    """the checkpoint's model with its live weights, or (--swa) with the averaged ones a run with trainer.swa / trainer.weight_averaging wrote"""
+    if getattr(args, "swa", False):
+        from handwriting_line_generation_amd.generate import load_for_generation
+        return load_for_generation(args.checkpoint, gpu=config["gpu"], checkpoint=dict(checkpoint, config=config), averaged=True)[0]
+    import handwriting_line_generation_amd.model as models
+    model = getattr(models, config["arch"])(config["model"])
+    state = {k: v for k, v in checkpoint["state_dict"].items() if "style_from_normal" not in k}
+    model.load_state_dict(state)
+    return model
+
+
 def setup(args):
     """checkpoint -> (config, trainer, training loader, validation loader, what to evaluate, iteration): the model in eval mode inside a
     trainer built with resume=False, as the reference does (new_eval.py:52-192)"""
     import numpy as np
     import torch
     torch.set_num_threads(1)
-    import handwriting_line_generation_amd.model as models
     import handwriting_line_generation_amd.model.loss as losses
     import handwriting_line_generation_amd.trainer as trainers
     from handwriting_line_generation_amd import evaluators
@@ -205,9 +217,7 @@ def setup(args):
     else:
         valid_data_loader, data_loader = getDataLoader(config, "test")
 
-    model = getattr(models, config["arch"])(config["model"])
-    state = {k: v for k, v in checkpoint["state_dict"].items() if "style_from_normal" not in k}
-    model.load_state_dict(state)
+    model = load_model(args, checkpoint, config)
     del checkpoint
     model.eval()
     if args.verbosity > 1 and hasattr(model, "summary"):

@@ -203,3 +203,92 @@ def unlayout(img, A, B):
 def sum_bound(terms, absval):
     """|err| <= terms * 2^-24 * (sum of absolute terms): a sum of rounded products / rounded partial sums, `terms` rounded operations deep"""
     return terms * 2.0 ** -24 * absval.double()
+
+
+# ---- weight gradients (hwg_conv_wgrad, hwg_wino_wgrad, hwg_colsum; tests/test_wgrad_ref_cpu.py holds these against autograd) ----------------
+# The operands are the C ABI's: u the ANCHOR tensor [N,P,Q,K], v the GATHERED one [N,H,W,C], g = dict(stride, pad, dil, R, S); the logical
+# gradient is dw [R,S,K,C]. A convolution layer has u = dy, v = x; a transposed layer u = x, v = dy (just another descriptor).
+def gathered(v, g, P, Q, r, s):
+    """v[n, p*sh - ph + r*dh, q*sw - pw + s*dw, :] for every anchor pixel, zero outside the image: [N,P,Q,C]"""
+    N, H, W, C = v.shape
+    (sh, sw), (ph, pw), (dh, dw) = g["stride"], g["pad"], g["dil"]
+    Hp = max(H + 2 * ph, (P - 1) * sh + dh * (g["R"] - 1) + 1)
+    Wp = max(W + 2 * pw, (Q - 1) * sw + dw * (g["S"] - 1) + 1)
+    vp = v.new_zeros((N, Hp, Wp, C))
+    vp[:, ph:ph + H, pw:pw + W] = v
+    return vp[:, r * dh:r * dh + (P - 1) * sh + 1:sh, s * dw:s * dw + (Q - 1) * sw + 1:sw]
+
+
+def wgrad_direct(u, v, g, dw0=None, absolute=False, ranges=None):
+    """dw[r,s,k,c] = sum_m u[m,k] v[gather(m,r,s),c] (+ dw0). ranges: None, or (begin, end) ranges of the anchor pixels m = (n,p,q), summed one
+    after the other as separate images (what the pixel split does) - the value is the same, the fp32 rounding differs"""
+    if absolute:
+        u, v = u.abs(), v.abs()
+    N, P, Q, K = u.shape
+    C, R, S = v.shape[3], g["R"], g["S"]
+    M = N * P * Q
+    um = u.reshape(M, K)
+    cols = [gathered(v, g, P, Q, r, s).reshape(M, C) for r in range(R) for s in range(S)]
+    dw = None
+    for m0, m1 in (ranges or [(0, M)]):
+        part = torch.stack([um[m0:m1].t() @ col[m0:m1] for col in cols]).reshape(R, S, K, C)
+        dw = part if dw is None else dw + part
+    if dw0 is not None:
+        dw = dw + (dw0.abs() if absolute else dw0).to(dw.dtype)
+    return dw
+
+
+def wgrad_terms(g, N, P, Q, H, W):
+    """[R,S,1,1] (fp64): the anchor pixels whose tap (r,s) falls inside the image - the contraction length of dw[r,s]"""
+    one = torch.ones(N, P, Q, 1, dtype=torch.float64)
+    return wgrad_direct(one, torch.ones(N, H, W, 1, dtype=torch.float64), g)
+
+
+def colsum(u, db0=None, absolute=False):
+    """the column sums of u [..., K] (the fused bias gradient; hwg_colsum) (+ db0)"""
+    if absolute:
+        u = u.abs()
+    out = u.reshape(-1, u.shape[-1]).sum(0)
+    if db0 is not None:
+        out = out + (db0.abs() if absolute else db0).to(out.dtype)
+    return out
+
+
+def _wino_wgrad_tiles(dy, xv, pad, m, BT, G, AT, absolute):
+    """the stride-1 weight gradient of r x r taps (r = 5 - m) over m x m gradient tiles, as csrc/conv_wino_wgrad.hip: Z = A dY A^T (4x4 from
+    the m x m tile of dy, A = AT^T), V = B^T d B (4x4 input patch), dU = sum over tiles Z . V, dg = G^T dU G: -> [r,r,K,Cv]"""
+    if absolute:
+        dy, xv = dy.abs(), xv.abs()
+    N, P, Q, K = dy.shape
+    H, W, C = xv.shape[1:]
+    TP, TQ = -(-P // m), -(-Q // m)
+    dyp = dy.new_zeros((N, TP * m, TQ * m, K))
+    dyp[:, :P, :Q] = dy
+    t = dyp.reshape(N, TP, m, TQ, m, K)                                  # [n, tp, a, tq, b, k]
+    xp = xv.new_zeros((N, max(H + 2 * pad[0], m * TP + 4 - m), max(W + 2 * pad[1], m * TQ + 4 - m), C))
+    xp[:, pad[0]:pad[0] + H, pad[1]:pad[1] + W] = xv
+    d = xp.unfold(1, 4, m).unfold(2, 4, m)[:, :TP, :TQ]                  # [n, tp, tq, c, 4, 4]
+    Am, Bm, Gm = _mat(AT, dy, absolute).t(), _mat(BT, dy, absolute), _mat(G, dy, absolute)
+    Z = torch.einsum("ia,ntaqbk->ntqkib", Am, t)
+    Z = torch.einsum("jb,ntqkib->ntqkij", Am, Z)
+    V = torch.einsum("ia,ntqcab->ntqcib", Bm, d)
+    V = torch.einsum("jb,ntqcib->ntqcij", Bm, V)
+    dU = torch.einsum("ntqkij,ntqcij->ijkc", Z, V)
+    out = torch.einsum("ir,ijkc->rjkc", Gm, dU)
+    return torch.einsum("js,rjkc->rskc", Gm, out)
+
+
+def wino_wgrad(dy, x, g, dw0=None, absolute=False):
+    """hwg_wino_wgrad: 3x3 stride 1 dilation 1 as F(3x3 taps, 2x2 gradient tiles); 4x4 stride 2 pad 0 as F(2x2 taps, 3x3 gradient tiles) on the
+    virtual input [N,P+1,Q+1,4C] (space to depth), virtual channel (a,b,c) of tap (u,v) being tap (2u+a, 2v+b) of the 4x4 filter: -> [R,S,K,C]"""
+    N, P, Q, K = dy.shape
+    C = x.shape[3]
+    if g["R"] == 3:
+        dw = _wino_wgrad_tiles(dy, x, g["pad"], 2, BT_23, G_23, AT_23, absolute)
+    else:
+        assert g["R"] == 4 and g["stride"] == (2, 2) and g["pad"] == (0, 0)
+        d2 = _wino_wgrad_tiles(dy, space_to_depth(x, P, Q), (0, 0), 3, BT_32, G_32, AT_32, absolute)      # [u, v, K, (a,b,c)]
+        dw = d2.reshape(2, 2, K, 2, 2, C).permute(0, 3, 1, 4, 2, 5).reshape(4, 4, K, C)
+    if dw0 is not None:
+        dw = dw + (dw0.abs() if absolute else dw0).to(dw.dtype)
+    return dw

@@ -3,7 +3,7 @@ conv_split_reduce_kernel, the C == 1 kernels conv_c1_rows / conv_c1_mfma / conv_
 hwg_wino_conv_fwd (every tile config, uniform split, balanced schedule with both reduce bodies), hwg_wino_s2_conv (forward and data gradient)
 and the weight-image entries - against the fp64 direct form of oracle/conv_ref.py, through L.call on the C ABI (never through ops.conv2d),
 every schedule forced through ops.tuning (case tables and the regimes they cover: oracle/conv_cases.py; the restatements, the tables and
-their sensitivity to seeded flaws are checked on the CPU by tests/test_conv_ref_cpu.py). The weight-gradient families are not covered here.
+their sensitivity to seeded flaws are checked on the CPU by tests/test_conv_ref_cpu.py). The weight-gradient families are held to the same protocol by tests/test_wgrad_fp64_gpu.py.
 
 Every call runs on buffers carved out of one allocation with 64-float canaries before, between and after x, the weight image, the bias, y
 and the workspace. The workspace has exactly the bytes the entry's *_workspace query returns and is filled with NaN before every call, y is

@@ -215,6 +215,42 @@ __global__ void loss_bwd_kernel(const float* a, const float* b, long long n, int
   }
 }
 
+// Foreground-masked L1 (trainer/hw_with_style_trainer.py:596-601: L1Loss(recon * fg_mask, image * fg_mask)): the term is |fl(r m) - fl(x m)|,
+// each product rounded to fp32 before the difference as the reference's two multiplications are. r, x: [rows][W]; the mask [rows][Wm],
+// Wm <= W, columns >= Wm count as 0 (the reference's F.pad(fg_mask, (0, toPad), value=0) without the copy). Same grid, element order and
+// partial layout as loss_partial_kernel mode 0, so a mask of ones gives the bits of the unmasked loss. No fused multiply-adds (block-scope pragmas).
+__device__ __forceinline__ float masked_l1_m(const float* mask, unsigned i, unsigned W, unsigned Wm) {
+  const unsigned row = i / W, col = i - row * W;
+  return col < Wm ? mask[(size_t)row * Wm + col] : 0.f;
+}
+__global__ __launch_bounds__(256) void masked_l1_partial_kernel(const float* r, const float* x, const float* mask, long long n, int W, int Wm,
+                                                                double* part) {
+#pragma clang fp contract(off)
+  __shared__ double sm[16];
+  double s = 0.0;
+  for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+    const float m = masked_l1_m(mask, (unsigned)i, (unsigned)W, (unsigned)Wm);
+    const float rm = r[i] * m, xm = x[i] * m;
+    s += (double)fabsf(rm - xm);
+  }
+  s = block_sum_d(s, sm);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+// d recon = sign(fl(r m) - fl(x m)) * m * (*gout) / n, 0 at ties (and so wherever m == 0); nothing flows to the image or the mask
+__global__ void masked_l1_bwd_kernel(const float* r, const float* x, const float* mask, long long n, int W, int Wm, const float* gout, float coef,
+                                     float* dr) {
+#pragma clang fp contract(off)
+  const float g = (*gout) * coef;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    const float m = masked_l1_m(mask, (unsigned)i, (unsigned)W, (unsigned)Wm);
+    const float rm = r[i] * m, xm = x[i] * m;
+    float d = (rm > xm) ? 1.f : ((rm < xm) ? -1.f : 0.f);
+    d *= m;
+    d *= g;
+    dr[i] = d;
+  }
+}
+
 // PixelNorm over the channel dim of [rows][C]: y = x / sqrt(mean(x^2) + 1e-8)  (model/pure_gen.py:306-311)
 __global__ __launch_bounds__(256) void pixelnorm_fwd_kernel(const float* x, float* y, int rows, int C, float eps) {
   const int lane = threadIdx.x & 63;
@@ -427,6 +463,33 @@ extern "C" int hwg_loss_bwd(const float* a, const float* b, long long n, int mod
   hipLaunchKernelGGL(loss_bwd_kernel, dim3(hwg_stream_grid(n, 256)), dim3(256), 0, (hipStream_t)stream, a, b, n, mode, grad_out, scale / (float)n, da, db,
                      accumulate);
   HWG_LAUNCH_CHECK("loss_bwd");
+  return HWG_OK;
+}
+
+extern "C" int hwg_masked_l1_fwd(const float* recon, const float* image, const float* mask, long long rows, int W, int Wm, float* out, void* ws,
+                                 size_t ws_bytes, void* stream) {
+  HWG_REQUIRE(recon && image && mask && out && rows > 0 && W > 0, "masked_l1_fwd: bad arguments");
+  HWG_REQUIRE(Wm >= 0 && Wm <= W, "masked_l1_fwd: mask width %d outside [0, %d]", Wm, W);
+  HWG_REQUIRE(rows * W < (1LL << 31), "masked_l1_fwd: %lld x %d elements, need fewer than 2^31", rows, W);
+  if (!ws || ws_bytes < hwg_loss_workspace()) { hwg_set_error("masked_l1_fwd: workspace too small"); return HWG_ERR_WORKSPACE; }
+  hipStream_t st = (hipStream_t)stream;
+  const long long n = rows * W;
+  const int np = dot_parts(n);
+  hipLaunchKernelGGL(masked_l1_partial_kernel, dim3(np), dim3(256), 0, st, recon, image, mask, n, W, Wm, (double*)ws);
+  HWG_LAUNCH_CHECK("masked_l1_partial");
+  hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(64), 0, st, (const double*)ws, np, 1.0 / (double)n, 1.f, out, 0);
+  HWG_LAUNCH_CHECK("masked_l1_final");
+  return HWG_OK;
+}
+extern "C" int hwg_masked_l1_bwd(const float* recon, const float* image, const float* mask, long long rows, int W, int Wm, const float* grad_out,
+                                 float* d_recon, void* stream) {
+  HWG_REQUIRE(recon && image && mask && grad_out && d_recon && rows > 0 && W > 0, "masked_l1_bwd: bad arguments");
+  HWG_REQUIRE(Wm >= 0 && Wm <= W, "masked_l1_bwd: mask width %d outside [0, %d]", Wm, W);
+  HWG_REQUIRE(rows * W < (1LL << 31), "masked_l1_bwd: %lld x %d elements, need fewer than 2^31", rows, W);
+  const long long n = rows * W;
+  hipLaunchKernelGGL(masked_l1_bwd_kernel, dim3(hwg_stream_grid(n, 256)), dim3(256), 0, (hipStream_t)stream, recon, image, mask, n, W, Wm, grad_out,
+                     1.f / (float)n, d_recon);
+  HWG_LAUNCH_CHECK("masked_l1_bwd");
   return HWG_OK;
 }
 

@@ -11,8 +11,8 @@ pixel exists): PIL bicubic (a = -0.5, antialiased) for the height normalisation 
 PIL bilinear for the affine warp. What IS pinned to the reference (tests/golden/getitem_calls.json): which pixels are decoded and cropped,
 the resize / warp geometry handed to the interpolator, output sizes, normalisation 1 - p/128, padding, label encoding, grouping of an
 author's lines and the draw order of the augmentation parameters. `fg_mask` (Otsu threshold + dilation through cv2 when `fg_masks_dir` is
-set, reference :407-420) is not produced: the key is absent from the items, as it is in the reference without `fg_masks_dir`; nothing on the
-loss path reads it (INTEGRATION.md lists the difference).
+set, reference :190-220, :407-420) is produced when the foreground-only loss is on (data/fg_masks.py: the masks are computed on the GPU and
+cached in the reference's files); otherwise the key is absent from the items, as it is in the reference without `fg_masks_dir`.
 """
 import json
 import math
@@ -70,17 +70,23 @@ def _resize(img, percent):
     return np.asarray(Image.fromarray(img).resize((w, h), Image.BICUBIC))
 
 
-def affine_trans(img, skew, strech):
+def affine_trans(img, skew, strech, fg_mask=None):
     """horizontal stretch + shear around the mid-line (augmentation.affine_trans): x' = strech*x + tan(skew)*(y - h/2), white border.
     cv2.warpAffine maps pixel INDICES (dst(x', y') = src(M^-1 (x', y'))); PIL evaluates its destination -> source map at pixel CENTRES
-    (x' + 0.5, y' + 0.5) and takes 0.5 off the result, so the constant term is moved by 0.5 (1 - A - B) to sample the same source positions."""
+    (x' + 0.5, y' + 0.5) and takes 0.5 off the result, so the constant term is moved by 0.5 (1 - A - B) to sample the same source positions.
+    With `fg_mask` (float32 [H, W]) -> (line, mask): the mask goes through the same map, bilinear on floats, border 0 (the reference's
+    warpAffine(fg_mask, ..., borderValue=0))."""
     from PIL import Image
     m = math.tan(skew)
     h = img.shape[0] / 2
     size = (int(img.shape[1] * strech), img.shape[0])
     A, B, C = 1.0 / strech, -m / strech, h * m / strech      # PIL wants the destination -> source map (index convention so far)
     coeffs = (A, B, C + 0.5 * (1.0 - A - B), 0.0, 1.0, 0.0)
-    return np.asarray(Image.fromarray(img).transform(size, Image.AFFINE, coeffs, resample=Image.BILINEAR, fillcolor=255))
+    out = np.asarray(Image.fromarray(img).transform(size, Image.AFFINE, coeffs, resample=Image.BILINEAR, fillcolor=255))
+    if fg_mask is None:
+        return out
+    warped = Image.fromarray(np.ascontiguousarray(fg_mask, dtype=np.float32), mode="F").transform(size, Image.AFFINE, coeffs, resample=Image.BILINEAR, fillcolor=0)
+    return out, np.asarray(warped, dtype=np.float32)
 
 
 class AuthorHWDataset(torch.utils.data.Dataset):
@@ -90,9 +96,7 @@ class AuthorHWDataset(torch.utils.data.Dataset):
         self.batch_size = config["a_batch_size"]          # lines per item (the reference's naming)
         self.no_spaces = config.get("no_spaces", False)
         self.max_width = config.get("max_width", 3000)
-        for key in ("triplet", "style_loc", "spaced_loc", "fg_masks_dir", "include_stroke_aug", "remove_bg"):
-            if key == "fg_masks_dir":
-                continue     # only read by the (unreachable) no_bg_loss branch
+        for key in ("triplet", "style_loc", "spaced_loc", "include_stroke_aug", "remove_bg"):       # (fg_masks_dir: _init_fg_masks)
             if config.get(key):
                 raise NotImplementedError("data option %r is not used by the shipped GAN configs" % key)
         sets = None
@@ -151,6 +155,34 @@ class AuthorHWDataset(torch.utils.data.Dataset):
         self.max_strech = 0.4
         self.max_rot_rad = 45 / 180 * math.pi
         self._pages = {}
+        self._init_fg_masks(config, split)
+
+    def _init_fg_masks(self, config, split):
+        """`fg_masks_dir` alone changes nothing (the shipped configs set it, and without the loss that reads the masks the reference's
+        items carry a key nobody looks at). getDataLoader adds `no_bg_loss` to the dataset's config when the trainer's switch is on
+        (fg_masks.wants_fg_masks) together with the device that computes what the cache lacks; a dataset constructed directly finds a
+        complete cache or refuses - there is no CPU execution of the mask kernel.
+        The reference names a mask `<author>_<line index among the author's lines OF THIS SPLIT>.png` and gives every split the same
+        directory: two splits that share a writer claim the same names for different lines (there the second split finds masks of the wrong
+        size and thresholds its lines anew in every __getitem__). `fg_mask_taken` (getDataLoader: the names the training split owns) sends
+        a later split that collides with them to `<fg_masks_dir>_<split>_<max_width>` instead; splits without a common writer - the
+        reference's layout as it is."""
+        self.fg_masks_dir = None
+        if not (config.get("no_bg_loss") and config.get("fg_masks_dir")):
+            return
+        from . import fg_masks
+        base, taken = config["fg_masks_dir"], config.get("fg_mask_taken")
+        if taken and not taken.isdisjoint(fg_masks._lines(self)):
+            base = "%s_%s" % (base[:-1] if base.endswith("/") else base, split if isinstance(split, str) else "_".join(split))
+        self.fg_masks_dir = fg_masks.cache_dir(base, self.max_width)
+        todo = fg_masks.missing(self)
+        if not todo:
+            return
+        device = config.get("fg_mask_device")
+        if device is None:
+            raise NotImplementedError("%d of this dataset's foreground masks are not in %s (first: %s_%d.png): construct the loader through "
+                                      "getDataLoader, which computes the missing ones on the GPU" % ((len(todo), self.fg_masks_dir) + todo[0]))
+        self.fg_mask_build = fg_masks.build_cache(self, device, todo)
 
     def __len__(self):
         return len(self.lineIndex)
@@ -211,11 +243,20 @@ class AuthorHWDataset(torch.utils.data.Dataset):
             images.append((line, gt, img))
         batch = []
         for line, gt, img in images:
+            fg = None
+            if self.fg_masks_dir is not None:
+                from . import fg_masks
+                fg = fg_masks.read_mask(fg_masks.mask_path(self, author, line))
+                assert fg.shape == img.shape, "foreground mask %s is %s, its line %s" % (fg_masks.mask_path(self, author, line), fg.shape, img.shape)
             if isinstance(self.augmentation, str) and "affine" in self.augmentation:
-                img = affine_trans(img, skew, strech)
+                if fg is None:
+                    img = affine_trans(img, skew, strech)
+                else:
+                    img, fg = affine_trans(img, skew, strech, fg)
+                    assert fg.shape == img.shape
             if len(gt) == 0:
                 return None
-            batch.append({"image": 1.0 - img.astype(np.float32)[..., None] / 128.0, "gt": gt,
+            batch.append({"image": 1.0 - img.astype(np.float32)[..., None] / 128.0, "gt": gt, "fg_mask": fg,
                           "gt_label": string_utils.str2label_single(gt, self.char_to_idx), "name": "%s_%d" % (author, line)})
         dim1 = max(b["image"].shape[1] for b in batch)
         images_t = np.full((len(batch), self.img_height, dim1, 1), PADDING_CONSTANT, dtype=np.float32)
@@ -225,9 +266,15 @@ class AuthorHWDataset(torch.utils.data.Dataset):
             images_t[i, :, :b["image"].shape[1], :] = b["image"]
             labels[:b["gt_label"].shape[0], i] = b["gt_label"]
         images_t = torch.from_numpy(images_t.transpose(0, 3, 1, 2))
-        return {"image": images_t, "mask": None, "top_and_bottom": None, "center_line": None, "label": torch.from_numpy(labels), "style": None,
+        item = {"image": images_t, "mask": None, "top_and_bottom": None, "center_line": None, "label": torch.from_numpy(labels), "style": None,
                 "label_lengths": torch.IntTensor([b["gt_label"].shape[0] for b in batch]), "gt": [b["gt"] for b in batch], "spaced_label": None,
                 "author": [author] * len(batch), "author_idx": [self.author_list.index(author)] * len(batch), "name": [b["name"] for b in batch]}
+        if self.fg_masks_dir is not None:
+            fg_t = np.zeros((len(batch), 1, self.img_height, dim1), dtype=np.float32)
+            for i, b in enumerate(batch):
+                fg_t[i, 0, :, :b["fg_mask"].shape[1]] = b["fg_mask"]
+            item["fg_mask"] = torch.from_numpy(fg_t)
+        return item
 
 
 def collate(batch):
@@ -364,8 +411,21 @@ def getDataLoader(config, split, rank=0, world=1):
         val.setdefault(k, v)
     wb = dl.get("width_bucket", 0)
     device = torch.device("cuda", int(config.get("gpu", 0) or 0)) if config.get("cuda", True) else None
+    # foreground-only reconstruction loss (data/fg_masks.py): off for every shipped config as it stands, and then nothing below differs
+    from . import fg_masks
+    fg_keys = {}
+    if "trainer" in config and fg_masks.loss_on(config):
+        if not dl.get("fg_masks_dir"):
+            raise ValueError("trainer.no_bg_loss is on (the config has a top-level no_bg_loss key) but data_loader.fg_masks_dir is not set: "
+                             "the foreground masks need a directory to be cached in")
+        if cls is DATASETS["HWDataset"]:
+            raise NotImplementedError("no_bg_loss: foreground masks are produced by the author-grouped line datasets only, not by HWDataset")
+        if device is None or not torch.cuda.is_available():
+            raise NotImplementedError('no_bg_loss with "cuda": false: the foreground masks are computed by a GPU kernel, there is no CPU execution')
+        fg_keys = {"no_bg_loss": True, "fg_mask_device": device}
 
     def build(part, cfg, *loader_args, **loader_kw):
+        cfg = dict(cfg, **fg_keys) if fg_keys else cfg
         variant = device_variant(dl["data_set_name"], cfg.get("augmentation"))
         if variant is None:
             return ShardedLoader(cls(dl["data_dir"], part, cfg), *loader_args, **loader_kw)
@@ -379,6 +439,8 @@ def getDataLoader(config, split, rank=0, world=1):
 
     if split == "train":
         tl = build("train", dl, dl["batch_size"], dl.get("shuffle", True), dl.get("num_workers", 1), rank, world, width_bucket=wb)
+        if fg_keys:
+            fg_keys["fg_mask_taken"] = frozenset(fg_masks._lines(tl.dataset))
         vl = build("valid", val, val.get("batch_size", dl["batch_size"]), val.get("shuffle", False), val.get("num_workers", 1), width_bucket=wb)
         return tl, (vl if len(vl.dataset) else None)
     return build(split, val, val.get("batch_size", dl["batch_size"]), False, val.get("num_workers", 1), width_bucket=wb), None

@@ -100,3 +100,4 @@ class AuthorRIMESLinesDataset(AuthorHWDataset):
         self.max_strech = 0.4
         self.max_rot_rad = 45 / 180 * math.pi
         self._pages = {}
+        self._init_fg_masks(config, split)

@@ -2029,6 +2029,46 @@ def mean_loss(a, mode=LOSS_MEAN, scale=1.0):
     return _Loss.apply(a.contiguous(), None, mode, scale)
 
 
+class _MaskedL1(Function):
+    @staticmethod
+    def forward(ctx, recon, image, mask):
+        B, _, H, W = recon.shape
+        out = torch.empty((), dtype=torch.float32, device=recon.device)
+        ws = workspace(L.query("hwg_loss_workspace"), recon.device)
+        L.call("hwg_masked_l1_fwd", recon, image, mask, B * H, W, mask.shape[3], out, ws, ws.numel(), _stream())
+        ctx.save_for_backward(recon, image, mask)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        recon, image, mask = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        B, _, H, W = recon.shape
+        dr = torch.empty_like(recon)
+        L.call("hwg_masked_l1_bwd", recon, image, mask, B * H, W, mask.shape[3], gout.contiguous(), dr, _stream())
+        return dr, None, None
+
+
+def masked_l1_loss(recon, image, mask):
+    """The foreground-only reconstruction loss (reference trainer :596-601): mean over all B*H*W elements of |recon * mask - image * mask|,
+    each product rounded to fp32 like the reference's two multiplications. recon, image [B,1,H,W]; mask [B,1,H,Wm] with Wm <= W, columns
+    >= Wm count as 0 (the reference pads the mask with zeros when it pads the image). A mask of ones gives the bits of l1_loss, value and
+    gradient. The gradient goes to `recon` only: image and mask are data."""
+    for t, name in ((recon, "masked_l1_loss recon"), (image, "masked_l1_loss image"), (mask, "masked_l1_loss mask")):
+        if not torch.is_tensor(t) or t.dim() != 4 or t.shape[1] != 1:
+            raise L.HwgError("%s must be a [B,1,H,W] tensor" % name)
+    recon, image, mask = recon.contiguous(), image.contiguous(), mask.contiguous()
+    _chk(recon, "masked_l1_loss recon"); _chk(image, "masked_l1_loss image"); _chk(mask, "masked_l1_loss mask")
+    if image.shape != recon.shape:
+        raise L.HwgError("masked_l1_loss: recon %s and image %s differ in shape" % (tuple(recon.shape), tuple(image.shape)))
+    if mask.shape[0] != recon.shape[0] or mask.shape[2] != recon.shape[2] or not (1 <= mask.shape[3] <= recon.shape[3]):
+        raise L.HwgError("masked_l1_loss: mask %s does not fit the images %s (same lines and rows, 1 <= Wm <= W)" % (tuple(mask.shape), tuple(recon.shape)))
+    if image.requires_grad or mask.requires_grad:
+        raise L.HwgError("masked_l1_loss: image and mask are data, no gradient flows to them")
+    return _MaskedL1.apply(recon, image, mask)
+
+
 # ----------------------------------------------------------------------------------------------
 # spectral norm
 # ----------------------------------------------------------------------------------------------
@@ -2511,6 +2551,46 @@ def lines_from_u8(pixels, offsets, widths, select, real=None, out=None, height=6
     L.call("hwg_lines_from_u8", pixels, pixels.numel(), table_d[:2 * m], table_d[2 * m:3 * m], int(used.size), table_d[3 * m:], int(sel.min()),
            real, Br, Wr, B, H, W, out, _stream())
     return out.view(-1)[:B * H * W].view(B, 1, H, W)
+
+
+def fg_masks(pixels, offsets, widths, height=64, out=None, want_thresholds=False):
+    """Foreground masks of a ragged pool of grey lines (csrc/fg_mask.hip; the reference's cv2 Otsu threshold, inversion and dilation with the
+    9 x 9 ellipse, datasets/author_hw_dataset.py:216-219) in one launch -> a uint8 pool of the same layout, 255 = foreground, 0 = not.
+    `pixels`: uint8 1-D device tensor; `offsets` [B+1] and `widths` [B] host arrays: line b is the row-major `height` x widths[b] picture at
+    pixels[offsets[b]:], offsets[B] = the bytes in use. Any width >= 1 and any byte offset; height <= 64. The host tables are validated here,
+    before anything is uploaded or launched. `out`: a uint8 device buffer of pixels' size to write into (only the lines' own bytes are
+    written; without one the bytes between the lines are 0). want_thresholds: -> (masks, int32 [B] device tensor of the Otsu levels)."""
+    import numpy as np
+    if not torch.is_tensor(pixels) or not pixels.is_cuda or pixels.dtype != torch.uint8 or pixels.dim() != 1 or not pixels.is_contiguous():
+        raise L.HwgError("fg_masks: pixels must be a contiguous 1-D uint8 device tensor")
+    H = int(height)
+    if not (1 <= H <= 64):
+        raise L.HwgError("fg_masks: line height %d, need 1..64" % H)
+    off = np.asarray(offsets, dtype=np.int64).reshape(-1)
+    w = np.asarray(widths, dtype=np.int64).reshape(-1)
+    B = w.shape[0]
+    if B < 1 or off.shape[0] != B + 1:
+        raise L.HwgError("fg_masks: %d offsets for %d widths, need one more" % (off.shape[0], B))
+    if ((w < 1) | (H * w > (1 << 22))).any():
+        raise L.HwgError("fg_masks: widths must lie in [1, %d], got %s" % ((1 << 22) // H, w.tolist()))
+    end = off[:B] + H * w
+    if (off[:B] < 0).any() or (end > off[B]).any() or off[B] > pixels.numel():
+        raise L.HwgError("fg_masks: every line must lie inside [0, offsets[B]) and offsets[B] inside the %d bytes of pixels, got %s" % (pixels.numel(), off.tolist()))
+    order = np.argsort(off[:B], kind="stable")
+    if (end[order][:-1] > off[:B][order][1:]).any():
+        raise L.HwgError("fg_masks: lines overlap, offsets %s widths %s" % (off.tolist(), w.tolist()))
+    if out is None:
+        out = torch.zeros_like(pixels)
+    elif (not torch.is_tensor(out) or not out.is_cuda or out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous()
+          or out.numel() < pixels.numel() or out.data_ptr() == pixels.data_ptr()):
+        raise L.HwgError("fg_masks: out must be a contiguous 1-D uint8 device buffer of at least %d bytes, not pixels itself" % pixels.numel())
+    table = np.empty(3 * B, dtype=np.int32)      # offsets [B] int64 first (8-byte aligned), then widths [B] int32: one upload
+    table[:2 * B].view(np.int64)[:] = off[:B]
+    table[2 * B:] = w
+    table_d = h2d(table, pixels.device)
+    thr = torch.empty((B,), dtype=torch.int32, device=pixels.device) if want_thresholds else None
+    L.call("hwg_fg_masks", pixels, pixels.numel(), table_d[:2 * B], table_d[2 * B:], B, H, out, thr, _stream())
+    return (out, thr) if want_thresholds else out
 
 
 # ----------------------------------------------------------------------------------------------

@@ -26,6 +26,7 @@ from . import flat_params as flat_params_mod
 from .flat_params import allreduce_gradient_sets, start_stash_allreduce
 from ..data.text_data import TextData
 from ..model.autoencoder import Encoder2
+from ..model import loss as loss_mod
 from ..model.hw_with_style import correct_pred
 from ..utils import string_utils
 
@@ -574,8 +575,15 @@ class HWWithStyleTrainer(BaseTrainer):
             elif recon.size(3) < image.size(3):
                 recon = _pad_w(recon, 0, image.size(3) - recon.size(3), "constant", PADDING_CONSTANT)
             if self.no_bg_loss:
-                raise NotImplementedError("fg-mask weighting is unreachable with the shipped configs (key read from the wrong level)")
-            losses["autoLoss"] = self.loss["auto"](recon, image, **self.loss_params["auto"])
+                # foreground only (:596-601): L1Loss(recon * fg_mask, image * fg_mask) as one kernel pair; the mask keeps the collated width,
+                # the columns `image` was padded by above count as 0 (the reference pads the mask with zeros there)
+                if self.loss["auto"] is not loss_mod.L1Loss or self.loss_params["auto"]:
+                    raise NotImplementedError("no_bg_loss: the foreground-masked reconstruction loss is implemented for L1Loss without parameters")
+                if instance.get("fg_mask") is None:
+                    raise KeyError("no_bg_loss is on but the batch carries no 'fg_mask': build the loader with getDataLoader and data_loader.fg_masks_dir")
+                losses["autoLoss"] = ops.masked_l1_loss(recon, image, ops.h2d(instance["fg_mask"], self.gpu))
+            else:
+                losses["autoLoss"] = self.loss["auto"](recon, image, **self.loss_params["auto"])
 
         if "count" in lesson and "count" in self.loss and "eval" not in lesson:
             if "auto" not in lesson:

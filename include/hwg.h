@@ -367,6 +367,17 @@ int hwg_loss_fwd(const float* a, const float* b, long long n, int mode, float sc
                  void* stream);
 int hwg_loss_bwd(const float* a, const float* b, long long n, int mode, float scale, const float* grad_out, float* da, float* db,
                  int accumulate, void* stream);
+/* Foreground-masked L1 of the GAN trainer's `no_bg_loss` (trainer/hw_with_style_trainer.py:596-601: L1Loss(recon * fg_mask, image * fg_mask)).
+ * recon, image: [rows][W] fp32 (rows = B * H); mask: [rows][Wm] fp32 with 1 <= Wm <= W, columns >= Wm count as 0 (the reference's
+ * F.pad(fg_mask, (0, toPad), value=0), not copied). rows * W < 2^31.
+ * _fwd: *out = mean over all rows * W elements of |fl(r m) - fl(x m)| (both products rounded to fp32, no fused multiply-add), summed in the
+ *   partial layout and order of hwg_loss_fwd mode 0 (same workspace): a mask of ones gives that call's bits. Two launches.
+ * _bwd: d_recon = sign(fl(r m) - fl(x m)) * m * *grad_out / (rows * W), 0 at ties; every element is written. One launch. Image and mask
+ *   are data: no gradient. */
+int hwg_masked_l1_fwd(const float* recon, const float* image, const float* mask, long long rows, int W, int Wm, float* out, void* ws,
+                      size_t ws_bytes, void* stream);
+int hwg_masked_l1_bwd(const float* recon, const float* image, const float* mask, long long rows, int W, int Wm, const float* grad_out,
+                      float* d_recon, void* stream);
 int hwg_pixelnorm_fwd(const float* x, float* y, int rows, int C, float eps, void* stream);
 int hwg_pixelnorm_bwd(const float* dy, const float* x, float* dx, int rows, int C, float eps, void* stream);
 /* scaled[i] = weights[i] * *x_i and *sum = their left-to-right sum (x_ptrs: HOST array of n <= 16 device addresses of scalars, weights: HOST
@@ -552,6 +563,22 @@ int hwg_lines_to_u8(const float* img, int B, int H, int W, const int* widths, co
  * without reading anything through it. */
 int hwg_lines_from_u8(const unsigned char* pixels, long long pixel_bytes, const long long* offsets, const int* widths, int n_lines,
                       const int* select, int min_select, const float* real, int Br, int Wr, int B, int H, int W, float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Foreground masks of grey lines (csrc/fg_mask.hip; datasets/author_hw_dataset.py:197-220: cv2.threshold(BINARY + OTSU), 255 - that,
+ * cv2.dilate with getStructuringElement(MORPH_ELLIPSE, (9, 9)) - there per line on the host).
+ * pixels (uint8, pixel_bytes of them), offsets [B] int64 and widths [B] int32 on the device: line b is the row-major H x widths[b] picture
+ * at pixels + offsets[b]; any width >= 1 and any byte offset. out: a pool of the same layout (a different buffer); line b's bytes become
+ * 255 (foreground) or 0, no other byte of out is written. Threshold t per line: the Otsu level of hwg_augment_stats (256-bin histogram in
+ * exact integers, (s0 w1 - s1 w0)^2 / (w0 w1) with the square and the quotient each rounded once in fp64, lowest level on ties, 0 for a
+ * constant line); foreground p <= t; dilated by the 57-cell ellipse (half-widths 0 3 3 4 4 4 3 3 0 for dy = -4 .. 4), pixels outside the
+ * line never count. thresholds (optional): [B] int32, t per line. One launch, one workgroup per line, no atomics.
+ * Checked here: no NULL, out != pixels, B > 0, 1 <= H <= 64. The tables are the caller's to check (device arrays: ops.fg_masks validates
+ * them on the host before the upload - widths >= 1, H * width <= 2^22 for the exact sums, every line inside the pool, no two lines
+ * overlapping); the kernel skips a line whose entry lies outside pixel_bytes (threshold -1) without touching anything.
+ * ------------------------------------------------------------------------------------------ */
+int hwg_fg_masks(const unsigned char* pixels, long long pixel_bytes, const long long* offsets, const int* widths, int B, int H,
+                 unsigned char* out, int* thresholds, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * The stretch film's labels (csrc/stretch.hip; generate.py:830-852 interpolate_horz: per frame a dense one-hot, permute(1,2,0),

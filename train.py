@@ -49,6 +49,10 @@ def main():
         config = load_checkpoint(resume)["config"]
     else:
         raise SystemExit("need -c or -r")
+    from handwriting_line_generation_amd.data import fg_masks
+    if args.synthetic and config["trainer"].get("class") != "AutoTrainer" and fg_masks.loss_on(config):
+        raise SystemExit("no_bg_loss is on (top-level key + trainer.no_bg_loss) but --synthetic batches carry no foreground masks: "
+                         "train on a dataset directory with data_loader.fg_masks_dir, or drop the top-level no_bg_loss key")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))

@@ -396,7 +396,10 @@ def getDataLoader(config, split, rank=0, world=1):
     An `augmentation` value the reference answers with Tensmeyer brightness + mesh warp (the two recogniser pre-training configs: true /
     "warp") is executed on the GPU on the collated batch: the dataset is constructed un-augmented and its loader wrapped in
     device_augment.DeviceAugment - per config, so the validation loader (which inherits `augmentation`, data_loaders.py:19-21) is wrapped
-    too. Every other value takes the path it always took."""
+    too. Every other value takes the path it always took.
+    `data_loader.device_store: true` (optional, not in the reference; the author-grouped datasets only) keeps the split's fitted lines in
+    GPU memory and produces every batch with one launch (line_store.StoreLoader); `data_loader.device_store_cache: <dir>` keeps the decoded
+    pool on disk. The validation config inherits both keys as it inherits every other."""
     from .device_augment import DeviceAugment, device_variant
     dl = config["data_loader"]
     if not DATASETS:
@@ -423,10 +426,21 @@ def getDataLoader(config, split, rank=0, world=1):
         if device is None or not torch.cuda.is_available():
             raise NotImplementedError('no_bg_loss with "cuda": false: the foreground masks are computed by a GPU kernel, there is no CPU execution')
         fg_keys = {"no_bg_loss": True, "fg_mask_device": device}
+    # device-resident line store (data/line_store.py): opt-in, and without the key nothing below differs
+    stored = [cfg for cfg in ((dl, val) if split == "train" else (val,)) if cfg.get("device_store")]
+    if stored:
+        from . import line_store
+        line_store.check_config(dl["data_set_name"], stored, device)
 
     def build(part, cfg, *loader_args, **loader_kw):
         cfg = dict(cfg, **fg_keys) if fg_keys else cfg
         variant = device_variant(dl["data_set_name"], cfg.get("augmentation"))
+        if cfg.get("device_store"):
+            from .line_store import StoreLoader
+            ds = cls(dl["data_dir"], part, cfg)
+            if not len(ds):
+                return ShardedLoader(ds, *loader_args, **loader_kw)
+            return StoreLoader(ds, *loader_args, device=device, cache_dir=cfg.get("device_store_cache"), **loader_kw)
         if variant is None:
             return ShardedLoader(cls(dl["data_dir"], part, cfg), *loader_args, **loader_kw)
         if device is None or not torch.cuda.is_available():      # there is no CPU execution of the brightness + warp augmentation

@@ -2594,6 +2594,126 @@ def fg_masks(pixels, offsets, widths, height=64, out=None, want_thresholds=False
 
 
 # ----------------------------------------------------------------------------------------------
+# GAN batches from a device-resident line store (csrc/line_store.hip, data/line_store.py)
+# ----------------------------------------------------------------------------------------------
+class LinePool:
+    """A ragged uint8 pool of fitted lines in GPU memory, the layout of fg_masks: `pixels` a contiguous 1-D uint8 device tensor, `offsets` /
+    `widths` host arrays [n] - line k is the row-major `height` x widths[k] picture at pixels[offsets[k]:], any width >= 1 and any byte
+    offset. `masks` (optional): a second pool of the same layout and size, bytes 0 / 255. Nothing is checked or uploaded here: store_batch
+    validates the pool's tables on the host the first time it is handed the pool and keeps the device copies of the two tables with it."""
+
+    def __init__(self, pixels, offsets, widths, height=64, masks=None):
+        self.pixels, self.masks, self.height = pixels, masks, int(height)
+        self.offsets, self.widths = offsets, widths
+        self._tables = None
+
+    def __len__(self):
+        return len(self.widths)
+
+    def _prepare(self):
+        import numpy as np
+        if self._tables is not None:
+            return self._tables
+        px, H = self.pixels, self.height
+        if not torch.is_tensor(px) or not px.is_cuda or px.dtype != torch.uint8 or px.dim() != 1 or not px.is_contiguous() or px.numel() < 1:
+            raise L.HwgError("store_batch: the pool's pixels must be a contiguous non-empty 1-D uint8 device tensor")
+        mk = self.masks
+        if mk is not None and (not torch.is_tensor(mk) or mk.device != px.device or mk.dtype != torch.uint8 or mk.dim() != 1 or not mk.is_contiguous()
+                               or mk.numel() != px.numel()):
+            raise L.HwgError("store_batch: the mask pool must be a contiguous 1-D uint8 tensor on the pixels' device and of their size (%d bytes), got %s"
+                             % (px.numel(), "%s %s %s" % (tuple(mk.shape), mk.dtype, mk.device) if torch.is_tensor(mk) else type(mk)))
+        if H < 1:
+            raise L.HwgError("store_batch: line height %d" % H)
+        off = np.asarray(self.offsets, dtype=np.int64).reshape(-1)
+        w = np.asarray(self.widths, dtype=np.int64).reshape(-1)
+        n = w.shape[0]
+        if n < 1 or n >= (1 << 31) or off.shape[0] < n:
+            raise L.HwgError("store_batch: %d offsets for %d widths" % (off.shape[0], n))
+        off = off[:n]
+        if ((w < 1) | (w >= (1 << 31))).any():
+            raise L.HwgError("store_batch: widths must be at least 1, got %s" % w[(w < 1) | (w >= (1 << 31))][:8].tolist())
+        end = off + H * w
+        if (off < 0).any() or (end > px.numel()).any():
+            bad = np.nonzero((off < 0) | (end > px.numel()))[0][:8]
+            raise L.HwgError("store_batch: every line must lie inside the %d bytes of pixels; lines %s do not" % (px.numel(), bad.tolist()))
+        order = np.argsort(off, kind="stable")
+        if (end[order][:-1] > off[order][1:]).any():
+            bad = order[1:][end[order][:-1] > off[order][1:]][:8]
+            raise L.HwgError("store_batch: lines overlap (lines %s begin inside another)" % bad.tolist())
+        table = np.empty(3 * n, dtype=np.int32)      # offsets [n] int64 first (8-byte aligned), then widths [n] int32: one upload
+        table[:2 * n].view(np.int64)[:] = off
+        table[2 * n:] = w
+        table_d = h2d(table, px.device)
+        self._tables = (table_d[:2 * n], table_d[2 * n:], n)
+        return self._tables
+
+
+def store_batch(pool, rows, W=None, want_mask=False, out=None):
+    """One collated GAN batch from a LinePool in one launch (hwg_store_batch): `rows` = [(line, out_w, strech, m)] per output row - line
+    `line` of the pool stretched by `strech` and sheared by m = tan(skew) around the mid-line into `out_w` columns (the reference's
+    affine_trans: cv2.warpAffine, bilinear, border blended in), as 1 - level / 128, padded with -1 to W columns -> fp32 [B,1,H,W] on the
+    pool's device. W: default max(out_w); any positive integer, not rounded. want_mask: -> (image, fg_mask), the pool's masks through the
+    same map (border 0, padded with 0). Everything is validated here on the host, before anything is uploaded or launched; then the row
+    tables go up in one pinned buffer (one h2d) and one launch on the current stream writes every element. `out`: a contiguous 16-byte
+    aligned fp32 device buffer of at least B*H*W rounded up to 4 elements to write into (with want_mask a pair of them); the returned
+    tensors are views of it."""
+    import numpy as np
+    if not isinstance(pool, LinePool):
+        raise L.HwgError("store_batch: pool must be an ops.LinePool, got %s" % type(pool))
+    off_d, w_d, n = pool._prepare()
+    H, dev = pool.height, pool.pixels.device
+    if want_mask and pool.masks is None:
+        raise L.HwgError("store_batch: want_mask, but the pool has no masks")
+    try:
+        r = np.asarray([tuple(x) for x in rows], dtype=np.float64)
+    except (TypeError, ValueError) as e:
+        raise L.HwgError("store_batch: rows must be (line, out_w, strech, m) tuples: %s" % e)
+    if r.ndim != 2 or r.shape[0] < 1 or r.shape[1] != 4:
+        raise L.HwgError("store_batch: rows must be a non-empty list of (line, out_w, strech, m), got shape %s" % (r.shape,))
+    B = r.shape[0]
+    line, ow, strech, m = r[:, 0], r[:, 1], r[:, 2], r[:, 3]
+    if not (np.isfinite(line).all() and (line == np.floor(line)).all() and (line >= 0).all() and (line < n).all()):
+        raise L.HwgError("store_batch: line indices must be integers in [0, %d), got %s" % (n, line.tolist()))
+    if not (np.isfinite(ow).all() and (ow == np.floor(ow)).all() and (ow >= 0).all() and (ow < (1 << 31)).all()):
+        raise L.HwgError("store_batch: out_w must be integers >= 0, got %s" % ow.tolist())
+    if W is None:
+        W = int(ow.max())
+    W = int(W)
+    if W < 1:
+        raise L.HwgError("store_batch: batch width %d, need at least 1" % W)
+    if (ow > W).any():
+        raise L.HwgError("store_batch: out_w %s above the batch width %d" % (ow[ow > W].tolist(), W))
+    if not (np.isfinite(strech).all() and (strech > 0).all()):
+        raise L.HwgError("store_batch: strech must be finite and positive, got %s" % strech.tolist())
+    if not np.isfinite(m).all():
+        raise L.HwgError("store_batch: m (tan of the skew) must be finite, got %s" % m.tolist())
+    total = B * H * W
+    need = -(-total // 4) * 4
+    if need >= (1 << 62):
+        raise L.HwgError("store_batch: a batch of %d x %d x %d elements" % (B, H, W))
+    outs = list(out) if isinstance(out, (tuple, list)) else [out] + ([None] if want_mask else [])
+    if len(outs) != (2 if want_mask else 1):
+        raise L.HwgError("store_batch: out must be %s" % ("a pair (image buffer, mask buffer)" if want_mask else "one buffer"))
+    for i, o in enumerate(outs):
+        if o is None:
+            outs[i] = torch.empty((need,), dtype=torch.float32, device=dev)
+        elif (not torch.is_tensor(o) or o.device != dev or o.dtype != torch.float32 or not o.is_contiguous() or o.numel() < need or o.data_ptr() % 16):
+            raise L.HwgError("store_batch: out must be a contiguous 16-byte aligned fp32 buffer on the pool's device of at least %d elements "
+                             "(B*H*W = %d rounded up to 4)" % (need, total))
+    elems = min(o.numel() for o in outs)
+    table = np.empty(6 * B, dtype=np.int32)      # strech [B], m [B] fp64 first (8-byte aligned), then line [B], out_w [B] int32: one upload
+    table[:2 * B].view(np.float64)[:] = strech
+    table[2 * B:4 * B].view(np.float64)[:] = m
+    table[4 * B:5 * B] = line.astype(np.int64)
+    table[5 * B:] = ow.astype(np.int64)
+    t = h2d(table, dev)
+    L.call("hwg_store_batch", pool.pixels, pool.masks if want_mask else None, pool.pixels.numel(), off_d, w_d, n, t[4 * B:5 * B], t[5 * B:],
+           t[:2 * B], t[2 * B:4 * B], B, H, W, outs[0], outs[1] if want_mask else None, elems, _stream())
+    res = [o.view(-1)[:total].view(B, 1, H, W) for o in outs]
+    return (res[0], res[1]) if want_mask else res[0]
+
+
+# ----------------------------------------------------------------------------------------------
 # sample sheets of GAN training: a batch of lines as one 8-bit grey picture (csrc/sample_sheet.hip)
 # ----------------------------------------------------------------------------------------------
 def sample_sheet_shape(B, H, W, nrow=None):

@@ -581,6 +581,31 @@ int hwg_fg_masks(const unsigned char* pixels, long long pixel_bytes, const long 
                  unsigned char* out, int* thresholds, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * GAN batches from a device-resident line store (csrc/line_store.hip; datasets/author_hw_dataset.py:386-470 __getitem__ + :27-112 collate
+ * with utils/augmentation.py:61-72 affine_trans - there on the host per line read from disk, through cv2.warpAffine).
+ * pixels: a ragged uint8 pool in the layout of hwg_fg_masks - offsets [n_lines] int64 and widths [n_lines] int32 on the device, line k the
+ * row-major H x widths[k] picture at pixels + offsets[k], any width >= 1 and any byte offset. masks (optional): a second pool of the same
+ * layout and size, bytes 0 / 255. Per output row b, device tables: line[b] int32 (which line), out_w[b] int32 (columns it fills),
+ * strech[b] and m[b] fp64 (horizontal stretch; m = tan(skew), computed on the host).
+ * One launch writes every element of out [B][1][H][W] fp32 and, with masks, of out_mask [B][1][H][W] fp32; W is any positive integer.
+ * fp64 without contraction, in this order: h = H / 2.0; sx = ((double)x - m * ((double)y - h)) / strech; x0 = floor(sx); f = sx - x0;
+ * p0, p1 = the bytes at columns x0, x0 + 1 of row y of the line, or the border value outside [0, widths[k]) (255 for lines, 0 for masks:
+ * cv2.warpAffine's constant border, blended into the edge pixels); v = p0 + f * (p1 - p0).
+ * Line: level = clamp(floor(v + 0.5), 0, 255), element 1 - level / 128 (exact in fp32). Mask: p = byte / 255, element (float)v.
+ * Columns x >= out_w[b]: -1 in out, 0 in out_mask. strech = 1, m = 0 reproduces the line's bytes.
+ * A lane owns 4 consecutive floats of the flat output (one 16-byte store per tensor, byte loads from the pool); out_elems: the floats out
+ * (and out_mask) hold, at least B*H*W rounded up to 4 - the surplus elements of the last word are written as padding, none beyond them.
+ * Checked here before the launch: no NULL, masks and out_mask both given or both absent, B, H, W, n_lines, pixel_bytes > 0, out / out_mask
+ * 16-byte aligned, the tables aligned to their element, B*H*W in 64 bits, out_elems. The tables are the caller's to check (device arrays:
+ * ops.store_batch validates them on the host before the upload - line in [0, n_lines), 0 <= out_w <= W, strech finite and positive, m
+ * finite, every line inside pixel_bytes, no two lines overlapping); the kernel turns a row whose entry is bad all the same into padding
+ * without reading anything through it.
+ * ------------------------------------------------------------------------------------------ */
+int hwg_store_batch(const unsigned char* pixels, const unsigned char* masks, long long pixel_bytes, const long long* offsets,
+                    const int* widths, int n_lines, const int* line, const int* out_w, const double* strech, const double* m, int B, int H,
+                    int W, float* out, float* out_mask, long long out_elems, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * The stretch film's labels (csrc/stretch.hip; generate.py:830-852 interpolate_horz: per frame a dense one-hot, permute(1,2,0),
  * F.interpolate(scale_factor=s, mode='linear'), permute(2,0,1) - 79 times per film).
  * label [T][B] int32: the aligned line (generate.py:298 correct_pred), blanks 0. frames: a device array of F records. Frame f is the

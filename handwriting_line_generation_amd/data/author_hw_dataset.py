@@ -399,7 +399,9 @@ def getDataLoader(config, split, rank=0, world=1):
     too. Every other value takes the path it always took.
     `data_loader.device_store: true` (optional, not in the reference; the author-grouped datasets only) keeps the split's fitted lines in
     GPU memory and produces every batch with one launch (line_store.StoreLoader); `data_loader.device_store_cache: <dir>` keeps the decoded
-    pool on disk. The validation config inherits both keys as it inherits every other."""
+    pool on disk. `data_loader.device_store: "warp"` is the store for the configs DeviceAugment serves (HWDataset and the author datasets
+    with a brightness + warp `augmentation`): the same batches, bit for bit, from one launch over the stored bytes. The validation config
+    inherits these keys as it inherits every other."""
     from .device_augment import DeviceAugment, device_variant
     dl = config["data_loader"]
     if not DATASETS:
@@ -418,6 +420,9 @@ def getDataLoader(config, split, rank=0, world=1):
     from . import fg_masks
     fg_keys = {}
     if "trainer" in config and fg_masks.loss_on(config):
+        if any(cfg.get("device_store") == "warp" for cfg in ((dl, val) if split == "train" else (val,))):
+            from .line_store import REFUSAL_WARP_MASKS
+            raise NotImplementedError(REFUSAL_WARP_MASKS)
         if not dl.get("fg_masks_dir"):
             raise ValueError("trainer.no_bg_loss is on (the config has a top-level no_bg_loss key) but data_loader.fg_masks_dir is not set: "
                              "the foreground masks need a directory to be cached in")
@@ -437,10 +442,12 @@ def getDataLoader(config, split, rank=0, world=1):
         variant = device_variant(dl["data_set_name"], cfg.get("augmentation"))
         if cfg.get("device_store"):
             from .line_store import StoreLoader
-            ds = cls(dl["data_dir"], part, cfg)
+            warp = cfg["device_store"] == "warp"               # (check_config: then `variant` is "full" or "low")
+            ds = cls(dl["data_dir"], part, dict(cfg, augmentation=None) if warp else cfg)
             if not len(ds):
                 return ShardedLoader(ds, *loader_args, **loader_kw)
-            return StoreLoader(ds, *loader_args, device=device, cache_dir=cfg.get("device_store_cache"), **loader_kw)
+            return StoreLoader(ds, *loader_args, device=device, cache_dir=cfg.get("device_store_cache"), variant=variant if warp else None,
+                               **loader_kw)
         if variant is None:
             return ShardedLoader(cls(dl["data_dir"], part, cfg), *loader_args, **loader_kw)
         if device is None or not torch.cuda.is_available():      # there is no CPU execution of the brightness + warp augmentation

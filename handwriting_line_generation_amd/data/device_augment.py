@@ -42,6 +42,44 @@ def line_extents(image):
     return np.where(has, first, 0), np.where(has, last - first + 1, 0)
 
 
+def mesh_from_extents(variant, H, x_off, widths):
+    """the variant's lattices for lines of height H with these extents (the "low" variant's coin flips: two per line, in line order)"""
+    from .. import ops
+    if variant == "low":
+        bright, warp = [], []
+        for _ in range(len(widths)):
+            bright.append(random.random() > 0.1)
+            warp.append(random.random() > 0.01)
+        return ops.LineMesh(H, widths, sigma=0.7, x_off=x_off, warp=warp, bright=bright)
+    return ops.LineMesh(H, widths, sigma=1.5, x_off=x_off)
+
+
+def host_draws(mesh):
+    """host rng mode: numpy's global generator in the reference's order per line (fg / bg, all row displacements, all column
+    displacements) -> fg_bg [B,2]; the displacements become mesh.disp"""
+    from .. import ops
+    fg_bg, disp = [], []
+    for b, src in enumerate(mesh.src):
+        fg_bg.append(np.random.normal(0, ops.AUG_BRIGHT_SIGMA, size=2))
+        if src is None:
+            disp.append(None)
+            continue
+        n = (len(src[0]), len(src[1]))
+        dy = np.random.normal(0.0, mesh.sigma[b], size=n)
+        disp.append((dy, np.random.normal(0.0, mesh.sigma[b], size=n)))
+    mesh.disp = disp
+    return np.asarray(fg_bg)
+
+
+def augment_batch(dev_image, mesh):
+    """the device batch `dev_image` [B,1,H,W] re-lit and warped over `mesh` -> a new device tensor (two launches); the draws are the device
+    generator's, or numpy's in host mode"""
+    from .. import ops, rng
+    if rng.mode() == "device":
+        return ops.augment_lines(dev_image, mesh, rng=rng.device_rng())
+    return ops.augment_lines(dev_image, mesh, fg_bg=host_draws(mesh))
+
+
 class DeviceAugment:
     """iterates `loader`; every batch's "image" is uploaded, augmented on the GPU and handed on as a device tensor (the trainers' `_to_tensor`
     passes device tensors through). `.dataset`, `.batch_size` and `len()` are the wrapped loader's."""
@@ -69,32 +107,12 @@ class DeviceAugment:
 
     def mesh_from_extents(self, H, x_off, widths):
         """the variant's lattices for lines of height H with these extents (the "low" variant's coin flips: two per line, in line order)"""
-        from .. import ops
-        if self.variant == "low":
-            bright, warp = [], []
-            for _ in range(len(widths)):
-                bright.append(random.random() > 0.1)
-                warp.append(random.random() > 0.01)
-            return ops.LineMesh(H, widths, sigma=0.7, x_off=x_off, warp=warp, bright=bright)
-        return ops.LineMesh(H, widths, sigma=1.5, x_off=x_off)
+        return mesh_from_extents(self.variant, H, x_off, widths)
 
     def augment(self, dev_image, mesh):
         """the uploaded batch `dev_image` [B,1,H,W] re-lit and warped over `mesh` -> a new device tensor (two launches); the draws are the
         device generator's, or numpy's in host mode"""
-        from .. import ops, rng
-        if rng.mode() == "device":
-            return ops.augment_lines(dev_image, mesh, rng=rng.device_rng())
-        fg_bg, disp = [], []
-        for b, src in enumerate(mesh.src):
-            fg_bg.append(np.random.normal(0, ops.AUG_BRIGHT_SIGMA, size=2))
-            if src is None:
-                disp.append(None)
-                continue
-            n = (len(src[0]), len(src[1]))
-            dy = np.random.normal(0.0, mesh.sigma[b], size=n)
-            disp.append((dy, np.random.normal(0.0, mesh.sigma[b], size=n)))
-        mesh.disp = disp
-        return ops.augment_lines(dev_image, mesh, fg_bg=np.asarray(fg_bg))
+        return augment_batch(dev_image, mesh)
 
     def apply(self, instance):
         from .. import ops

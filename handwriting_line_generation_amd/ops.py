@@ -2606,6 +2606,7 @@ class LinePool:
         self.pixels, self.masks, self.height = pixels, masks, int(height)
         self.offsets, self.widths = offsets, widths
         self._tables = None
+        self._stats = None                                     # store_line_stats: (thr, hist), computed once
 
     def __len__(self):
         return len(self.widths)
@@ -2711,6 +2712,101 @@ def store_batch(pool, rows, W=None, want_mask=False, out=None):
            t[:2 * B], t[2 * B:4 * B], B, H, W, outs[0], outs[1] if want_mask else None, elems, _stream())
     res = [o.view(-1)[:total].view(B, 1, H, W) for o in outs]
     return (res[0], res[1]) if want_mask else res[0]
+
+
+def store_line_stats(pool):
+    """The per-line statistics of the brightness augmentation for a whole LinePool, once (hwg_store_line_stats, one launch, one workgroup
+    per line) -> (thr int32 [n], hist int32 [n, 256]) on the pool's device, kept with the pool: the Otsu level of augment_lines' statistics
+    and the 256-bin histogram depend on the stored bytes alone. The pool's tables are validated on the host first (LinePool._prepare, and
+    height x width <= 2^22 for the exact sums)."""
+    import numpy as np
+    if not isinstance(pool, LinePool):
+        raise L.HwgError("store_line_stats: pool must be an ops.LinePool, got %s" % type(pool))
+    if pool._stats is not None:
+        return pool._stats
+    off_d, w_d, n = pool._prepare()
+    H, dev = pool.height, pool.pixels.device
+    w = np.asarray(pool.widths, dtype=np.int64).reshape(-1)[:n]
+    if (H * w > (1 << 22)).any():
+        raise L.HwgError("store_line_stats: lines of more than 2^22 pixels (height %d, widths %s) are too large for the exact Otsu sums"
+                         % (H, w[H * w > (1 << 22)][:8].tolist()))
+    thr = torch.empty((n,), dtype=torch.int32, device=dev)
+    hist = torch.empty((n, 256), dtype=torch.int32, device=dev)
+    L.call("hwg_store_line_stats", pool.pixels, pool.pixels.numel(), off_d, w_d, n, H, thr, hist, _stream())
+    pool._stats = (thr, hist)
+    return pool._stats
+
+
+def store_warp_batch(pool, lines, mesh, W=None, fg_bg=None, want_map=False, rng=None, out=None):
+    """One augmented recogniser batch from a LinePool in one launch (hwg_store_warp_batch): output row b shows line lines[b] of the pool,
+    re-lit and warped over `mesh` (a LineMesh of the pool's height whose widths are those lines' widths; mesh.x_off places a line inside
+    the row, columns outside it are -1) -> fp32 [B,1,H,W] on the pool's device, W default max(x_off + width). The result equals
+    augment_lines on the same lines collated and uploaded, bit for bit; the draws are consumed as there: fg_bg None - unit draws of `rng`
+    (a DeviceRNG: one hwg_randn launch of (B, 2 + 2 GY GX), the stream offset advances); fg_bg [B,2] (host) - explicit shifts with the
+    explicit displacements of mesh.disp. want_map: -> (y, map [B,2,H,W]). Everything is validated here on the host before anything is
+    uploaded or launched; the row tables go up in one pinned buffer. `out`: a contiguous fp32 buffer on the pool's device of at least
+    B*H*W elements to write into; the returned tensor is a view of it."""
+    import numpy as np
+    if not isinstance(pool, LinePool):
+        raise L.HwgError("store_warp_batch: pool must be an ops.LinePool, got %s" % type(pool))
+    if not isinstance(mesh, LineMesh):
+        raise L.HwgError("store_warp_batch: mesh must be an ops.LineMesh, got %s" % type(mesh))
+    off_d, w_d, n = pool._prepare()
+    thr, hist = store_line_stats(pool)
+    H, dev = pool.height, pool.pixels.device
+    try:
+        k = np.asarray(lines, dtype=np.float64).reshape(-1)
+    except (TypeError, ValueError) as e:
+        raise L.HwgError("store_warp_batch: lines must be pool line indices: %s" % e)
+    B = k.shape[0]
+    if B < 1 or B > 65535 or B != len(mesh.widths):
+        raise L.HwgError("store_warp_batch: %d lines for a mesh of %d rows (1..65535 rows)" % (B, len(mesh.widths)))
+    if not (np.isfinite(k).all() and (k == np.floor(k)).all() and (k >= 0).all() and (k < n).all()):
+        raise L.HwgError("store_warp_batch: line indices must be integers in [0, %d), got %s" % (n, k.tolist()))
+    k = k.astype(np.int64)
+    if mesh.H != H:
+        raise L.HwgError("store_warp_batch: a mesh for lines of height %d over a pool of height %d" % (mesh.H, H))
+    mw, xo = np.asarray(mesh.widths, dtype=np.int64), np.asarray(mesh.x_off, dtype=np.int64)
+    pw = np.asarray(pool.widths, dtype=np.int64).reshape(-1)[k]
+    if (mw != pw).any():
+        raise L.HwgError("store_warp_batch: the mesh's widths %s are not the widths %s of the pool's lines %s" % (mw.tolist(), pw.tolist(), k.tolist()))
+    if W is None:
+        W = int((xo + mw).max())
+    W = int(W)
+    if W < 1 or W >= (1 << 31):
+        raise L.HwgError("store_warp_batch: batch width %d" % W)
+    if (xo < 0).any() or (xo + mw > W).any():
+        raise L.HwgError("store_warp_batch: line extents (x_off %s, widths %s) outside the batch width %d" % (xo.tolist(), mw.tolist(), W))
+    if mesh.GY > 16:
+        raise L.HwgError("store_warp_batch: a lattice of %d rows (at most 16: lines up to ~190 px high)" % mesh.GY)
+    if (fg_bg is None) != (mesh.disp is None):
+        raise L.HwgError("store_warp_batch: explicit brightness draws and explicit displacements go together")
+    if fg_bg is not None:
+        fg_bg = np.asarray(fg_bg, dtype=np.float64)
+        if fg_bg.shape != (B, 2) or not np.isfinite(fg_bg).all():
+            raise L.HwgError("store_warp_batch: fg_bg must be %d finite pairs, got shape %s" % (B, fg_bg.shape))
+    elif rng is None:
+        raise L.HwgError("store_warp_batch: no explicit draws and no device generator")
+    total = B * H * W
+    if out is None:
+        out = torch.empty((total,), dtype=torch.float32, device=dev)
+    elif not torch.is_tensor(out) or out.device != dev or out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < total:
+        raise L.HwgError("store_warp_batch: out must be a contiguous fp32 buffer on the pool's device of at least %d elements" % total)
+    li, lf, dr = mesh.tables(fg_bg)
+    lfs, drs = lf.shape[1], 2 + 2 * mesh.GY * mesh.GX
+    table = np.empty(B * (5 + lfs + (0 if dr is None else drs)), dtype=np.int32)      # line [B], lines_i [B,4], lines_f, draws: one upload
+    table[:B] = k
+    table[B:5 * B] = li.reshape(-1)
+    table[5 * B:5 * B + B * lfs].view(np.float32)[:] = lf.reshape(-1)
+    if dr is not None:
+        table[5 * B + B * lfs:].view(np.float32)[:] = dr.reshape(-1)
+    t = h2d(table, dev)
+    draws = rng.randn((B, drs), dev) if dr is None else t[5 * B + B * lfs:]
+    map_out = torch.empty((B, 2, H, W), dtype=torch.float32, device=dev) if want_map else None
+    L.call("hwg_store_warp_batch", pool.pixels, pool.pixels.numel(), off_d, w_d, n, thr, hist, t[:B], t[B:5 * B], t[5 * B:5 * B + B * lfs], lfs,
+           draws, drs, B, H, W, mesh.GY, mesh.GX, out, map_out, out.numel(), _stream())
+    y = out.view(-1)[:total].view(B, 1, H, W)
+    return (y, map_out) if want_map else y
 
 
 # ----------------------------------------------------------------------------------------------

@@ -606,6 +606,36 @@ int hwg_store_batch(const unsigned char* pixels, const unsigned char* masks, lon
                     int W, float* out, float* out_mask, long long out_elems, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Recogniser pre-training batches from the device-resident line store (csrc/store_warp.hip): the brightness + mesh warp of
+ * hwg_augment_stats / hwg_augment_warp executed on the bytes of the pool (the layout of hwg_store_batch: pixels, offsets [n_lines] int64,
+ * widths [n_lines] int32 on the device) instead of on an uploaded, collated fp32 batch. The arithmetic is that of the two entry points above,
+ * from the same source (csrc/augment_warp.h): a batch through hwg_store_warp_batch equals the same lines collated, uploaded and put through
+ * hwg_augment_stats + hwg_augment_warp with the same tables, bit for bit, padding included.
+ * hwg_store_line_stats: once per pool, one workgroup per line -> thr [n_lines] int32, the Otsu level of hwg_augment_stats (exact integer
+ *   sums, fp64 between-class variance, lowest level on ties), and hist [n_lines][256] int32, the line's histogram. Both depend on the
+ *   stored bytes alone. H * width <= 2^22 (the exact sums) is the caller's to check with the rest of the pool's tables
+ *   (ops.store_line_stats, on the host); a line whose entry lies outside pixel_bytes gets thr -1 and an empty histogram, nothing is read.
+ * hwg_store_warp_batch: one launch writes every element of out [B][1][H][W] (and of map_out [B][2][H][W], optional, tests; NaN outside
+ *   the mesh / the line), W any positive integer. Per output row b: line[b] int32, the pool line it shows, and the tables of
+ *   hwg_augment_warp - lines_i [B][4] = {w = widths[line[b]], gy, gx, x_off}, lines_f [B][lf_stride], draws [B][draw_stride], GY / GX the
+ *   batch's largest lattice. One workgroup per row x 64 columns: LUT[256] in LDS from thr[line[b]] and the row's two draws (identity for
+ *   scales or draws of 0: a row whose brightness is off), the border level round-half-even(sum hist * LUT / (H w)) by an exact integer
+ *   reduction, then the lattice / diagonal / barycentric / bilinear path of hwg_augment_warp with taps LUT[pool byte]. Columns outside
+ *   [x_off, x_off + w) are -1; rows with gy = 0, H <= 5 or w <= 5 get the LUT alone.
+ *   Checked here before the launch: no NULL (map_out may be), B, H, W, n_lines, pixel_bytes > 0, B <= 65535, 0 <= GY <= 16, GX >= 0, the
+ *   strides against the lattice, the tables and outputs aligned to their element, B*H*W in 64 bits and <= out_elems (the floats out holds).
+ *   The tables are the caller's to check (device arrays: ops.store_warp_batch validates them on the host before the upload); the kernel
+ *   turns a row whose entry is bad all the same - line outside [0, n_lines), a line outside pixel_bytes, w != widths[line], x_off < 0 or
+ *   x_off + w > W - into padding without reading anything through it.
+ * ------------------------------------------------------------------------------------------ */
+int hwg_store_line_stats(const unsigned char* pixels, long long pixel_bytes, const long long* offsets, const int* widths, int n_lines, int H,
+                         int* thr, int* hist, void* stream);
+int hwg_store_warp_batch(const unsigned char* pixels, long long pixel_bytes, const long long* offsets, const int* widths, int n_lines,
+                         const int* thr, const int* hist, const int* line, const int* lines_i, const float* lines_f, int lf_stride,
+                         const float* draws, int draw_stride, int B, int H, int W, int GY, int GX, float* out, float* map_out,
+                         long long out_elems, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * The stretch film's labels (csrc/stretch.hip; generate.py:830-852 interpolate_horz: per frame a dense one-hot, permute(1,2,0),
  * F.interpolate(scale_factor=s, mode='linear'), permute(2,0,1) - 79 times per film).
  * label [T][B] int32: the aligned line (generate.py:298 correct_pred), blanks 0. frames: a device array of F records. Frame f is the

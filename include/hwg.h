@@ -747,7 +747,9 @@ int hwg_writer_first_rank(const float* styles, const int* author_id, int N, int 
  * launch. Summation order of the recurrent dot product: fixed, documented at the top of csrc/lstm.hip (depends on H alone).
  * hwg_lstm_bwd walks t the other way: launch t forms dh_rec = dgates[t+-1] W_hh for its units from whh_t, the [2][H][4H] transposed image
  * written by hwg_lstm_pack_whh (once per weight epoch), then the gate backward, and writes dgates [2][T][B][4H] (= d xproj; its column sums
- * are d b_hh, dgates[d]^T hseq-rows[d] is d W_hh[d] - both through the existing kernels). dc_ws: [2][2][B][H] ping-pong workspace.
+ * are d b_hh, dgates[d]^T hseq-rows[d] is d W_hh[d] - both through the existing kernels). dc_ws: [2][2][B][H] ping-pong workspace, [slot][direction]: the launch of
+ * step n (n = 0 .. T-1 in the backward walk) writes dc_t f_t, the cell gradient handed to the next launch, to slot n & 1 and reads slot (n + 1) & 1;
+ * after the call slot (T - 1) & 1 holds the last launch's value and, for T >= 2, the other slot the one before it.
  * Limits, checked before any launch: T, B >= 1, H a multiple of hwg_lstm_unit_slice() and <= 1024, T*B*4H < 2^31; W_hh, y, dgates and whh_t
  * 16-byte aligned. A batch wider than hwg_lstm_batch_tile(H) lines (the LDS image, min(32, 16384 / H)) is walked in tiles of that many.
  * ------------------------------------------------------------------------------------------ */

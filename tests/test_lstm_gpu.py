@@ -22,19 +22,10 @@ import torch
 
 import _lstm_ref
 from _gpu_tidy import leave_nothing_behind  # noqa: F401  (module-scoped, autouse)
+from oracle.lstm_cases import make_case  # (the seeded draw, shared with tests/test_lstm_fp64_gpu.py)
 
 pytestmark = pytest.mark.gpu
 EPS = 2.0 ** -24
-
-
-def make_case(T, B, H, seed):
-    g = np.random.RandomState(seed)
-    s = 1.0 / np.sqrt(H)
-    c = dict(xp=[g.randn(T, B, 4 * H).astype(np.float32) for _ in range(2)],
-             w=[g.uniform(-s, s, (4 * H, H)).astype(np.float32) for _ in range(2)],
-             b=[g.uniform(-s, s, (4 * H,)).astype(np.float32) for _ in range(2)],
-             dy=g.randn(T, B, 2 * H).astype(np.float32))
-    return c
 
 
 def run_layer(c, dev, wgrad=True, training=True):

@@ -724,6 +724,8 @@ extern "C" int hwg_norm_fwd(const float* x, float* y, int N, int HW, int C, int 
   HWG_REQUIRE(x && y && mean && rstd, "norm_fwd: null pointer");
   HWG_REQUIRE(mode >= 0 && mode <= 2, "norm_fwd: bad mode %d", mode);
   if (mode == MODE_GN) HWG_REQUIRE(groups > 0 && C % groups == 0, "norm_fwd: C=%d not divisible by groups=%d", C, groups);
+  // batch statistics span the samples and the backward's finalize pass forms c1 / c2 / dgamma / dbeta per channel: no per-sample affine there
+  HWG_REQUIRE(mode != MODE_BN || !affine_per_sample, "norm_fwd: affine_per_sample is not defined for BatchNorm");
   Geo g = make_geo(N, HW, C);
   if (!ws || ws_bytes < hwg_norm_workspace(N, HW, C)) { hwg_set_error("norm_fwd: workspace too small"); return HWG_ERR_WORKSPACE; }
   hipStream_t st = (hipStream_t)stream;
@@ -761,6 +763,9 @@ extern "C" int hwg_norm_bwd(const float* dy, const float* x, const float* y, flo
   int rc = check_geo(N, HW, C, "norm_bwd");
   if (rc) return rc;
   HWG_REQUIRE(dy && x && dx && mean && rstd, "norm_bwd: null pointer");
+  HWG_REQUIRE(mode >= 0 && mode <= 2, "norm_bwd: bad mode %d", mode);
+  if (mode == MODE_GN) HWG_REQUIRE(groups > 0 && C % groups == 0, "norm_bwd: C=%d not divisible by groups=%d", C, groups);
+  HWG_REQUIRE(mode != MODE_BN || !affine_per_sample, "norm_bwd: affine_per_sample is not defined for BatchNorm");
   HWG_REQUIRE(act == 0 || act == HWG_ACT_RELU || act == HWG_ACT_LRELU || y, "norm_bwd: y required when tanh is fused");
   // relu / leaky relu: the gate is the sign of the forward pre-activation, recomputed from x, the statistics and the affine of the forward
   // call - two of the seven passes over the tensor (y in both sweeps) are not made

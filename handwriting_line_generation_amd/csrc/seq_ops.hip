@@ -371,7 +371,7 @@ extern "C" int hwg_ctc_fwd_beta(const float* log_probs, const int* targets, cons
 }
 static int ctc_bwd(const float* log_probs, const int* targets, const int* input_lengths, const int* target_lengths, int T, int B, int C, int Lmax,
                    const float* grad_out, float* grad, void* ws, size_t ws_bytes, void* stream, bool have_beta) {
-  HWG_REQUIRE(log_probs && targets && input_lengths && target_lengths && grad_out && grad, "ctc_bwd: bad arguments");
+  HWG_REQUIRE(log_probs && targets && input_lengths && target_lengths && grad_out && grad && T > 0 && B > 0 && C > 0 && Lmax > 0, "ctc_bwd: bad arguments");
   if (!ws || ws_bytes < hwg_ctc_workspace(T, B, Lmax)) { hwg_set_error("ctc_bwd: workspace too small"); return HWG_ERR_WORKSPACE; }
   hipStream_t st = (hipStream_t)stream;
   const size_t NS = 2 * (size_t)Lmax + 1;

@@ -459,7 +459,8 @@ extern "C" int hwg_loss_fwd(const float* a, const float* b, long long n, int mod
 }
 extern "C" int hwg_loss_bwd(const float* a, const float* b, long long n, int mode, float scale, const float* grad_out, float* da, float* db,
                             int accumulate, void* stream) {
-  HWG_REQUIRE(a && grad_out && n > 0 && (da || db), "loss_bwd: bad arguments");
+  HWG_REQUIRE(a && grad_out && n > 0 && (da || db) && mode >= 0 && mode <= 4, "loss_bwd: bad arguments");
+  HWG_REQUIRE(mode > 1 || b, "loss_bwd: pair loss needs b");
   hipLaunchKernelGGL(loss_bwd_kernel, dim3(hwg_stream_grid(n, 256)), dim3(256), 0, (hipStream_t)stream, a, b, n, mode, grad_out, scale / (float)n, da, db,
                      accumulate);
   HWG_LAUNCH_CHECK("loss_bwd");

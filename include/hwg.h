@@ -213,7 +213,8 @@ int hwg_colsum(const float* x, long long rows, int C, float* out, int accumulate
  * Normalisation + activation epilogues (NHWC, x is [N][HW][C]).
  * mode: 0 InstanceNorm, 1 GroupNorm(groups), 2 BatchNorm in training mode (batch statistics,
  * running stats updated with `momentum` when running_mean != NULL).
- * y = act(mask[n,c] * (gamma * xhat + beta)); gamma/beta are [C] or, with affine_per_sample, [N][C].
+ * y = act(mask[n,c] * (gamma * xhat + beta)); gamma/beta are [C] or, with affine_per_sample, [N][C] (dgamma / dbeta likewise; InstanceNorm
+ * and GroupNorm only: BatchNorm with affine_per_sample is refused).
  * Replaces nn.GroupNorm (+Dropout2d +ReLU/LeakyReLU) at model/discriminator_ap.py:78-79,103-104,
  * model/autoencoder.py:346-395,307-330, model/char_style.py:41,91,100,166, model/count_cnn.py:13-21;
  * nn.BatchNorm2d/1d at model/cnn_only_hwr.py:36,80-89; nn.InstanceNorm2d at model/pure_gen.py:56.

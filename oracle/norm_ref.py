@@ -70,6 +70,14 @@ def norm(x, mode, groups=1, gamma=None, beta=None, mask=None, act=ACT_NONE, slop
     return act_ref(norm_pre(x, mode, groups, gamma, beta, mask, eps), act, slope, hint)
 
 
+def norm_per_sample(x, mode, groups, gamma, beta, mask=None, act=ACT_NONE, slope=0.0, eps=1e-5, hint=None):
+    """InstanceNorm / GroupNorm with one affine per sample (affine_per_sample = 1 of hwg_norm_fwd / hwg_norm_bwd): gamma, beta [N, C],
+    y[n] = act(mask[n, c] * (gamma[n, c] * xhat[n] + beta[n, c])); autograd leaves d gamma, d beta as [N, C] - no sum over the samples.
+    Batch statistics with a per-sample affine are not defined (the entries refuse them)."""
+    assert mode in ("in", "gn") and gamma.shape == beta.shape == (x.shape[0], x.shape[1]), (mode, tuple(gamma.shape))
+    return norm(x, mode, groups, gamma, beta, mask, act, slope, eps, hint)
+
+
 def running_stats(x, running_mean, running_var, momentum):
     """BatchNorm's running statistics after one training-mode call on x [N, C, H, W] (new tensors)"""
     cnt = x.shape[0] * x.shape[2] * x.shape[3]

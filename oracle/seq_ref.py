@@ -25,6 +25,12 @@ def log_softmax_tbc(x):
     return (z - lse).permute(1, 0, 2)
 
 
+def log_softmax_rows(x):
+    """the same without the transpose (transpose_bt = 0 of hwg_log_softmax_fwd / _bwd): [B, 1, T, C] logits -> [B * T, C] log-probabilities,
+    rows in the input's own (b, t) order"""
+    return log_softmax_tbc(x).permute(1, 0, 2).reshape(-1, x.shape[-1])
+
+
 def _lse_rows(rows):
     """log(sum(exp(rows), dim 0)) of [k, n]; a column of -inf gives -inf and passes no gradient (no 0 * inf anywhere)"""
     m = rows.detach().max(dim=0).values
@@ -84,6 +90,12 @@ def loss(a, b, mode, scale):
     else:
         term = torch.where(1 + a > 0, 1 + a, zero)
     return scale * (term.sum() / term.numel())
+
+
+def loss_accumulate(out0, a, b, mode, scale):
+    """accumulate = 1 of hwg_loss_fwd: out0 + scale * mean(term). Backward with accumulate = 1 likewise adds to what da / db hold:
+    da0 + d loss / d a and db0 + d loss / d b (the latter is db0 - d loss / d a for the pair losses)."""
+    return out0 + loss(a, b, mode, scale)
 
 
 def spectral(w_bar, u, v, eps):

@@ -47,7 +47,7 @@ __global__ __launch_bounds__(FGM_BLOCK) void fg_mask_kernel(const unsigned char*
   const long long off = offsets[b];
   const int w = widths[b];
   // a bad table entry (ops.fg_masks refuses it on the host) touches nothing
-  if (w < 1 || off < 0 || off + (long long)H * w > pixel_bytes) {
+  if (!hwg_line_in_pool(off, w, H, pixel_bytes)) {
     if (thr_out && tid == 0) thr_out[b] = -1;
     return;
   }

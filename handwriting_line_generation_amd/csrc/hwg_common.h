@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <string.h>
 #include "../../include/hwg.h"
+#include "table_guard.h"      // the bounds of the device-resident tables: the only place they are written
 
 #define HWG_WAVE 64
 

@@ -49,7 +49,7 @@ __device__ __forceinline__ StoreRow store_row(int b, long long pixel_bytes, cons
   const int w = widths[k], ow = out_w[b];
   const long long off = offsets[k];
   const double s = strech[b], mm = m[b];
-  const bool ok = w >= 1 && off >= 0 && off <= pixel_bytes && (long long)H * w <= pixel_bytes - off && ow >= 0 && ow <= W &&
+  const bool ok = hwg_line_in_pool(off, w, H, pixel_bytes) && ow >= 0 && ow <= W &&
                   s > 0.0 && fabs(s) < INFINITY && fabs(mm) < INFINITY;      // (comparisons are false for NaN)
   if (!ok) return r;
   r.off = off; r.w = w; r.ow = ow; r.strech = s; r.m = mm;

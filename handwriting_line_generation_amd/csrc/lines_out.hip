@@ -49,8 +49,9 @@ extern "C" int hwg_lines_to_u8(const float* img, int B, int H, int W, const int*
 // arbitrary Wr (row stride and alignment are no multiples of 4): four scalar loads, one 16-byte store. Every level is exact in fp32
 // (p / 128 is a power-of-two scaling, 1 - q with q a multiple of 2^-7 below 2), so this IS the host's arithmetic.
 //
-// The caller validated the tables; an entry that is bad all the same (k >= n_lines, r >= Br, a line that ends behind pixel_bytes) makes
-// its row padding: nothing is read through it. All stores are inside out [B,1,H,W] whatever the tables hold.
+// The caller validated the tables; an entry that is bad all the same (k >= n_lines, r >= Br, a width that is no multiple of 4 or above W,
+// an offset that is negative or no multiple of 4, a line that ends behind pixel_bytes - hwg_line_in_pool of table_guard.h, for any 64-bit
+// offset) makes its row padding: nothing is read through it. All stores are inside out [B,1,H,W] whatever the tables hold.
 __global__ __launch_bounds__(LINES_BLOCK) void lines_from_u8_kernel(const unsigned char* __restrict__ pixels, long long pixel_bytes,
                                                                     const long long* __restrict__ offsets, const int* __restrict__ widths,
                                                                     int n_lines, const int* __restrict__ select, const float* __restrict__ real,
@@ -64,7 +65,7 @@ __global__ __launch_bounds__(LINES_BLOCK) void lines_from_u8_kernel(const unsign
     if (s < n_lines) {
       const int w = widths[s];
       const long long off = offsets[s];
-      const bool ok = w > 0 && w <= W && (w & 3) == 0 && off >= 0 && (off & 3) == 0 && off + (long long)H * w <= pixel_bytes;
+      const bool ok = w <= W && (w & 3) == 0 && (off & 3) == 0 && hwg_line_in_pool(off, w, H, pixel_bytes);
       if (ok && col < w) {
         const unsigned px = *(const unsigned*)(pixels + off + (size_t)y * w + col);
         v.x = 1.0f - (float)(px & 255u) / 128.0f;

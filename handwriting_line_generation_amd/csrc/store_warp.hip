@@ -31,7 +31,7 @@ __global__ __launch_bounds__(SLS_BLOCK) void store_line_stats_kernel(const unsig
   const long long off = offsets[b];
   const int w = widths[b];
   // a bad table entry (ops.store_line_stats refuses it on the host) reads nothing: threshold -1, empty histogram
-  if (w < 1 || off < 0 || off > pixel_bytes || (long long)H * w > pixel_bytes - off) {
+  if (!hwg_line_in_pool(off, w, H, pixel_bytes)) {
     if (tid == 0) thr_out[b] = -1;
     if (tid < 256) hist_out[(size_t)b * 256 + tid] = 0;
     return;
@@ -114,7 +114,7 @@ __global__ __launch_bounds__(256) void store_warp_kernel(const unsigned char* __
   if (k >= 0 && k < n_lines) {
     const int wk = widths[k], xo = lines_i[4 * b + 3];
     const long long o = offsets[k];
-    if (wk >= 1 && lines_i[4 * b] == wk && o >= 0 && o <= pixel_bytes && (long long)H * wk <= pixel_bytes - o && xo >= 0 && wk <= W && xo <= W - wk) {
+    if (lines_i[4 * b] == wk && hwg_line_in_pool(o, wk, H, pixel_bytes) && xo >= 0 && wk <= W && xo <= W - wk) {
       w = wk; xoff = xo; off = o;
     }
   }

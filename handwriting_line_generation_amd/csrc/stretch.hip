@@ -92,8 +92,7 @@ __global__ __launch_bounds__(STRETCH_BLOCK) void stretch_onehot_kernel(const int
   const hwg_stretch_frame fr = frames[blockIdx.y];
   if (fr.T_out < 1 || fr.T_out > max_T_out) return;
   const unsigned n = (unsigned)B * (unsigned)fr.T_out * (unsigned)ncls;      // < 2^31: checked at the entry point for max_T_out
-  if (fr.off_blc < 0 || (fr.off_blc & 3) || fr.off_blc + (long long)n > blc_elems) return;
-  if (fr.off_lbc < 0 || (fr.off_lbc & 3) || fr.off_lbc + (long long)n > lbc_elems) return;
+  if (!hwg_block_in_buffer(fr.off_blc, (long long)n, blc_elems) || !hwg_block_in_buffer(fr.off_lbc, (long long)n, lbc_elems)) return;
   const int identity = fr.identity && fr.T_out == T;      // (an identity frame of another length would read labels behind step T - 1)
   const unsigned quads = (n + 3u) / 4u;
   for (unsigned q = blockIdx.x * STRETCH_BLOCK + threadIdx.x; q < quads; q += gridDim.x * STRETCH_BLOCK) {

@@ -532,6 +532,9 @@ int hwg_insert_spaces_fill(const int* label, const int* label_lengths, const int
  *   that is locally Delaunay (what scipy.interpolate.griddata(destination, source, pixels, "linear") computes wherever every lattice
  *   triangle is a Delaunay triangle); pixels outside the mesh take m; lines with gy = 0, H <= 5 or w <= 5 get the LUT only
  *   (grid_distortion.py:12). map_out (optional, tests): [B][2][H][W] = (map_y, map_x) in line coordinates, NaN outside the mesh / the line.
+ * lines_i is a device array, the caller's to check (ops.augment_lines validates it on the host before the upload). Both entries CLAMP an
+ *   extent that is bad all the same rather than refusing the row: x_off' = max(x_off, 0), w' = max(min(w, W - x_off'), 0); the row is then
+ *   exactly the row of the table (w', x_off'), and nothing is read past the image row.
  * ------------------------------------------------------------------------------------------ */
 int hwg_augment_stats(const float* x, const int* lines_i, const float* lines_f, int lf_stride, const float* draws, int draw_stride,
                       int B, int H, int W, int* stats, void* stream);
@@ -545,7 +548,9 @@ int hwg_augment_warp(const float* x, const int* lines_i, const float* lines_f, i
  * picture out[offsets[b] : offsets[b] + H * widths[b]] (row stride widths[b]); columns >= widths[b] are never read.
  * Pixel: (1 - x) * 127.5 in fp32, clamped to [0, 255] (numpy wraps outside [-1, 1]), NaN -> 0, truncated toward zero.
  * W % 4 == 0 (checked here); 4 <= widths[b] <= W, widths[b] % 4 == 0 and offsets[b] % 4 == 0 are the caller's to check (device arrays:
- * ops.lines_to_u8 validates them on the host before the upload). One 16-byte load and one 32-bit store per lane.
+ * ops.lines_to_u8 validates them on the host before the upload). One 16-byte load and one 32-bit store per lane. A width that is bad all
+ * the same is CLAMPED, the row is not refused: the kernel works with w' = min(widths[b], W) & ~3 (nothing for w' <= 0) - row stride w',
+ * no read past the image row, no byte outside out[offsets[b] : offsets[b] + H * w'] written.
  * ------------------------------------------------------------------------------------------ */
 int hwg_lines_to_u8(const float* img, int B, int H, int W, const int* widths, const long long* offsets, unsigned char* out, void* stream);
 
@@ -560,8 +565,10 @@ int hwg_lines_to_u8(const float* img, int B, int H, int W, const int* widths, co
  * Checked here: no NULL, B, H, W > 0, W % 4 == 0, out 16-byte and pixels 4-byte aligned, Wr <= W, and min_select - the smallest entry of
  * select as the caller states it (the table itself is a device array) - not below -Br, i.e. not negative without a real batch. The tables
  * are the caller's to check (ops.lines_from_u8 validates them on the host before the upload); the kernel turns a row whose entry is bad
- * all the same (k >= n_lines, r >= Br, a width that is no multiple of 4 or above W, a line that ends behind pixel_bytes) into padding
- * without reading anything through it. */
+ * all the same (k >= n_lines, r >= Br, a width that is no multiple of 4 or above W, an offset that is negative or no multiple of 4, a line
+ * that ends behind pixel_bytes) into padding without reading anything through it. The bounds hold for ANY 64-bit offset: they are the
+ * predicates of csrc/table_guard.h, which never form off + H * w (that sum wraps for an offset near 2^63) but compare H * w with
+ * pixel_bytes - off. The same holds for every entry below that reads a pool or a frame table. */
 int hwg_lines_from_u8(const unsigned char* pixels, long long pixel_bytes, const long long* offsets, const int* widths, int n_lines,
                       const int* select, int min_select, const float* real, int Br, int Wr, int B, int H, int W, float* out, void* stream);
 
@@ -576,7 +583,9 @@ int hwg_lines_from_u8(const unsigned char* pixels, long long pixel_bytes, const 
  * line never count. thresholds (optional): [B] int32, t per line. One launch, one workgroup per line, no atomics.
  * Checked here: no NULL, out != pixels, B > 0, 1 <= H <= 64. The tables are the caller's to check (device arrays: ops.fg_masks validates
  * them on the host before the upload - widths >= 1, H * width <= 2^22 for the exact sums, every line inside the pool, no two lines
- * overlapping); the kernel skips a line whose entry lies outside pixel_bytes (threshold -1) without touching anything.
+ * overlapping); the kernel skips a line whose entry is bad all the same - width < 1, a negative offset, a line that ends behind
+ * pixel_bytes, for any 64-bit offset (csrc/table_guard.h) - with threshold -1 and without touching anything: no byte of out is written,
+ * the bytes the bad entry names included.
  * ------------------------------------------------------------------------------------------ */
 int hwg_fg_masks(const unsigned char* pixels, long long pixel_bytes, const long long* offsets, const int* widths, int B, int H,
                  unsigned char* out, int* thresholds, void* stream);
@@ -600,7 +609,7 @@ int hwg_fg_masks(const unsigned char* pixels, long long pixel_bytes, const long 
  * 16-byte aligned, the tables aligned to their element, B*H*W in 64 bits, out_elems. The tables are the caller's to check (device arrays:
  * ops.store_batch validates them on the host before the upload - line in [0, n_lines), 0 <= out_w <= W, strech finite and positive, m
  * finite, every line inside pixel_bytes, no two lines overlapping); the kernel turns a row whose entry is bad all the same into padding
- * without reading anything through it.
+ * (-1 in out, 0 in out_mask) without reading anything through it; "inside pixel_bytes" holds for any 64-bit offset (csrc/table_guard.h).
  * ------------------------------------------------------------------------------------------ */
 int hwg_store_batch(const unsigned char* pixels, const unsigned char* masks, long long pixel_bytes, const long long* offsets,
                     const int* widths, int n_lines, const int* line, const int* out_w, const double* strech, const double* m, int B, int H,
@@ -627,7 +636,8 @@ int hwg_store_batch(const unsigned char* pixels, const unsigned char* masks, lon
  *   strides against the lattice, the tables and outputs aligned to their element, B*H*W in 64 bits and <= out_elems (the floats out holds).
  *   The tables are the caller's to check (device arrays: ops.store_warp_batch validates them on the host before the upload); the kernel
  *   turns a row whose entry is bad all the same - line outside [0, n_lines), a line outside pixel_bytes, w != widths[line], x_off < 0 or
- *   x_off + w > W - into padding without reading anything through it.
+ *   x_off + w > W - into padding (NaN in map_out) without reading anything through it. Both entries: "outside pixel_bytes" holds for any
+ *   64-bit offset (csrc/table_guard.h).
  * ------------------------------------------------------------------------------------------ */
 int hwg_store_line_stats(const unsigned char* pixels, long long pixel_bytes, const long long* offsets, const int* widths, int n_lines, int H,
                          int* thr, int* hist, void* stream);
@@ -650,7 +660,9 @@ int hwg_store_warp_batch(const unsigned char* pixels, long long pixel_bytes, con
  * Checked here before the launch: no NULL, T, B, ncls, max_T_out >= 1, 1 <= F <= 65535, T < 2^23, B * max_T_out * ncls below 2^31,
  * buffers 16-byte aligned. The table is the caller's to check (ops.stretch_onehot validates it on the host before the upload, and the
  * labels: a class outside [0, ncls) is an error there); a record that is bad all the same - T_out outside [1, max_T_out], a misaligned
- * block or one that ends behind blc_elems / lbc_elems floats - writes nothing, and a label outside [0, ncls) matches no class.
+ * block, a negative offset or a block that ends behind blc_elems / lbc_elems floats, for any 64-bit offset (csrc/table_guard.h) - writes
+ * nothing to either buffer, and a label outside [0, ncls) matches no class. identity != 0 in a record whose T_out is not T is ignored:
+ * the frame is re-sampled like any other (an identity frame of another length would read labels behind step T - 1).
  * ------------------------------------------------------------------------------------------ */
 typedef struct hwg_stretch_frame {
   int T_out;                  /* steps of this frame                                   */

@@ -4,9 +4,6 @@ return); the fp64 restatements added for the paths no Python caller reaches - pe
 accumulating loss (oracle/seq_ref.loss_accumulate), the untransposed log-softmax (oracle/seq_ref.log_softmax_rows) - agree with the
 restatements they extend where the two must coincide; and plausible kernel flaws seeded into them (one sample's gamma used for all, out0
 dropped, rows left in (t, b) order) each move some case of the tables past the bound the GPU files hold it to by SENSITIVITY_FACTOR or more."""
-import importlib.util
-import os
-
 import pytest
 import torch
 
@@ -15,21 +12,12 @@ from oracle import norm_cases as NC
 from oracle import norm_ref as NR
 from oracle import seq_cases as SC
 from oracle import seq_ref as SR
+from _fp64 import SECOND, U, _f32, cpu_threads
+from _norm_act_checks import BOUNDS as NORM_BOUNDS, EPS, norm_inputs
+from _seq_loss_checks import ACC_CASES, BOUNDS as SEQ_BOUNDS
 
 SENSITIVITY_FACTOR = 10.0
-
-
-def _gpu_module(fname):
-    """a GPU test file's inputs, bounds and comparisons (importing it needs no GPU)"""
-    spec = importlib.util.spec_from_file_location(fname[:-3] + "_refs", os.path.join(os.path.dirname(os.path.abspath(__file__)), fname))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-GN = _gpu_module("test_norm_abi_fp64_gpu.py")
-GS = _gpu_module("test_seq_loss_abi_fp64_gpu.py")
-GN.NA._cpu_threads()
+cpu_threads()
 
 
 # ---- the tables ------------------------------------------------------------------------------------------------------------------------------------
@@ -88,7 +76,7 @@ def test_sequence_and_loss_tables_reach_every_regime():
     assert AC.LOSS_SIZES == [1, 255, 4096, 4097, 131072]
     assert {(c[1], c[2]) for c in AC.LOSS_CASES} == {(m, n) for m in range(5) for n in AC.LOSS_SIZES}
     assert {c[3] for c in AC.LOSS_CASES} == {1.0, -1.0} and {c[4] for c in AC.LOSS_CASES if c[1] < 2} == {"a", "b", "both"}
-    assert {c[1] for c in GS.ACC_CASES} == set(range(5)) and {c[4] for c in GS.ACC_CASES if c[1] < 2} >= {"b", "both"}
+    assert {c[1] for c in ACC_CASES} == set(range(5)) and {c[4] for c in ACC_CASES if c[1] < 2} >= {"b", "both"}
     assert [r * w for r, w, _ in AC.MASKED_L1_CASES] == [1, 255, 4097] and all(1 <= wm <= w and (wm < w or w == 1) for _, w, wm in AC.MASKED_L1_CASES)
     assert AC.SN_SHAPES[:3] == [(1, 1), (5, 7), (3, 4097)] and AC.SN_SHAPES[3] in SC.SN_MODEL_SHAPES
     assert all(AC.SN_SHAPES[3][0] * AC.SN_SHAPES[3][1] <= r * k for r, k in SC.SN_MODEL_SHAPES)
@@ -109,40 +97,40 @@ def _errs(got, want):
 @pytest.mark.parametrize("c", AC.PER_SAMPLE_CASES, ids=[c["name"] for c in AC.PER_SAMPLE_CASES])
 def test_per_sample_affine_restatement_and_one_gamma_for_all(c):
     N, C = c["N"], c["C"]
-    t = GN.norm_inputs(c)
+    t = norm_inputs(c)
     x, m = t["x"].double(), t["mask"].double() if t["mask"] is not None else None
-    shared = NR.norm(x, c["mode"], c["groups"], t["gamma"].double(), t["beta"].double(), m, c["act"], c["slope"], GN._f32(GN.EPS))
-    equal = NR.norm_per_sample(x, c["mode"], c["groups"], t["gamma"].double().expand(N, C), t["beta"].double().expand(N, C), m, c["act"], c["slope"], GN._f32(GN.EPS))
+    shared = NR.norm(x, c["mode"], c["groups"], t["gamma"].double(), t["beta"].double(), m, c["act"], c["slope"], _f32(EPS))
+    equal = NR.norm_per_sample(x, c["mode"], c["groups"], t["gamma"].double().expand(N, C), t["beta"].double().expand(N, C), m, c["act"], c["slope"], _f32(EPS))
     assert torch.equal(shared, equal)                         # every sample's affine equal to the shared one: the same function
-    td = GN.norm_inputs(dict(c, name=c["name"] + "/distinct"), per_sample=True)
+    td = norm_inputs(dict(c, name=c["name"] + "/distinct"), per_sample=True)
     x, m = td["x"].double(), td["mask"].double() if td["mask"] is not None else None
     g64, b64 = td["gamma"].double().requires_grad_(True), td["beta"].double().requires_grad_(True)
-    y = NR.norm_per_sample(x, c["mode"], c["groups"], g64, b64, m, c["act"], c["slope"], GN._f32(GN.EPS))
+    y = NR.norm_per_sample(x, c["mode"], c["groups"], g64, b64, m, c["act"], c["slope"], _f32(EPS))
     y.backward(td["gy"].double())
     assert g64.grad.shape == (N, C) and b64.grad.shape == (N, C)
     # and sample by sample it is the shared-affine function of that sample alone (IN / GN statistics do not cross samples)
     for n in range(N):
         mn = m[n:n + 1] if m is not None else None
-        one = NR.norm(x[n:n + 1], c["mode"], c["groups"], td["gamma"][n].double(), td["beta"][n].double(), mn, c["act"], c["slope"], GN._f32(GN.EPS))
+        one = NR.norm(x[n:n + 1], c["mode"], c["groups"], td["gamma"][n].double(), td["beta"][n].double(), mn, c["act"], c["slope"], _f32(EPS))
         assert torch.allclose(one, y[n:n + 1].detach(), rtol=0, atol=1e-12)
     # flaw: the kernel indexes gamma / beta with c instead of n * C + c - sample 0's affine serves every sample
-    flawed = NR.norm(x, c["mode"], c["groups"], td["gamma"][0].double(), td["beta"][0].double(), m, c["act"], c["slope"], GN._f32(GN.EPS))
+    flawed = NR.norm(x, c["mode"], c["groups"], td["gamma"][0].double(), td["beta"][0].double(), m, c["act"], c["slope"], _f32(EPS))
     rel, mx = _errs(flawed, y.detach())
-    print("\nper-sample %-28s one gamma for all: rel L2 %.2e max/max %.2e (bound %.1e, %.1e)" % ((c["name"], rel, mx) + GN.BOUNDS["norm_fwd"]))
-    assert rel >= SENSITIVITY_FACTOR * GN.BOUNDS["norm_fwd"][0] and mx >= SENSITIVITY_FACTOR * GN.BOUNDS["norm_fwd"][1]
+    print("\nper-sample %-28s one gamma for all: rel L2 %.2e max/max %.2e (bound %.1e, %.1e)" % ((c["name"], rel, mx) + NORM_BOUNDS["norm_fwd"]))
+    assert rel >= SENSITIVITY_FACTOR * NORM_BOUNDS["norm_fwd"][0] and mx >= SENSITIVITY_FACTOR * NORM_BOUNDS["norm_fwd"][1]
 
 
-@pytest.mark.parametrize("case", GS.ACC_CASES, ids=[c[0] for c in GS.ACC_CASES])
+@pytest.mark.parametrize("case", ACC_CASES, ids=[c[0] for c in ACC_CASES])
 def test_accumulating_loss_restatement_and_out0_dropped(case):
     name, mode, n, scale, wrt, inputs = case
     a, b = SC.loss_inputs(case)
     a64, b64 = a.double(), b.double() if b is not None else None
-    v = SR.loss(a64, b64, mode, GS._f32(scale))
-    assert SR.loss_accumulate(torch.zeros((), dtype=torch.float64), a64, b64, mode, GS._f32(scale)) == v
+    v = SR.loss(a64, b64, mode, _f32(scale))
+    assert SR.loss_accumulate(torch.zeros((), dtype=torch.float64), a64, b64, mode, _f32(scale)) == v
     out0 = (v * 0.75).float().double()
-    want = SR.loss_accumulate(out0, a64, b64, mode, GS._f32(scale))
+    want = SR.loss_accumulate(out0, a64, b64, mode, _f32(scale))
     k = 2 if mode == 1 else 1
-    bound = float((k * 2 * GS.U * v.abs() + GS.U * want.abs()) * GS.SECOND)
+    bound = float((k * 2 * U * v.abs() + U * want.abs()) * SECOND)
     # the bound is sound for an fp32 evaluation in the kernels' order: the mean rounded once, times scale, one rounded sum
     term = {0: (a - b).abs() if b is not None else None, 1: (a - b) * (a - b) if b is not None else None, 2: a, 3: (1 - a).clamp_min(0), 4: (1 + a).clamp_min(0)}[mode]
     v32 = (term.double().sum() / n).float() * torch.tensor(scale)
@@ -164,9 +152,9 @@ def test_untransposed_log_softmax_restatement_and_rows_left_in_tb_order(case):
     if B > 1 and T > 1:
         # flaw: transpose_bt = 0 ignored, the rows written in (t, b) order
         rel, mx = _errs(tbc.reshape(T * B, C), rows)
-        print("\nlog-softmax %-16s rows left in (t, b) order: rel L2 %.2e max/max %.2e (bound %.1e, %.1e)" % ((name, rel, mx) + GS.BOUNDS["lsm_fwd"]))
-        assert rel >= SENSITIVITY_FACTOR * GS.BOUNDS["lsm_fwd"][0] and mx >= SENSITIVITY_FACTOR * GS.BOUNDS["lsm_fwd"][1]
+        print("\nlog-softmax %-16s rows left in (t, b) order: rel L2 %.2e max/max %.2e (bound %.1e, %.1e)" % ((name, rel, mx) + SEQ_BOUNDS["lsm_fwd"]))
+        assert rel >= SENSITIVITY_FACTOR * SEQ_BOUNDS["lsm_fwd"][0] and mx >= SENSITIVITY_FACTOR * SEQ_BOUNDS["lsm_fwd"][1]
 
 
 def test_some_table_case_shows_each_flaw():
-    assert any(B > 1 and T > 1 for _, B, T, _, _ in AC.LOG_SOFTMAX_CASES) and GS.ACC_CASES and AC.PER_SAMPLE_CASES
+    assert any(B > 1 and T > 1 for _, B, T, _, _ in AC.LOG_SOFTMAX_CASES) and ACC_CASES and AC.PER_SAMPLE_CASES

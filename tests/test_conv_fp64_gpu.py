@@ -3,7 +3,8 @@ conv_split_reduce_kernel, the C == 1 kernels conv_c1_rows / conv_c1_mfma / conv_
 hwg_wino_conv_fwd (every tile config, uniform split, balanced schedule with both reduce bodies), hwg_wino_s2_conv (forward and data gradient)
 and the weight-image entries - against the fp64 direct form of oracle/conv_ref.py, through L.call on the C ABI (never through ops.conv2d),
 every schedule forced through ops.tuning (case tables and the regimes they cover: oracle/conv_cases.py; the restatements, the tables and
-their sensitivity to seeded flaws are checked on the CPU by tests/test_conv_ref_cpu.py). The weight-gradient families are held to the same protocol by tests/test_wgrad_fp64_gpu.py.
+their sensitivity to seeded flaws are checked on the CPU by tests/test_conv_ref_cpu.py). The buffers are those of tests/_guarded.py, the
+references, the bounds and check() those of tests/_conv_checks.py. The weight-gradient families are held to the same protocol by tests/test_wgrad_fp64_gpu.py.
 
 Every call runs on buffers carved out of one allocation with 64-float canaries before, between and after x, the weight image, the bias, y
 and the workspace. The workspace has exactly the bytes the entry's *_workspace query returns and is filled with NaN before every call, y is
@@ -35,104 +36,17 @@ absolute value). T is the contraction length of the engine, c counts the further
                                                                           2^-24 |G||g||G^T|; copies and padding    e/b 0.49 / 0.90
                                                                           exact
 (measured: worst |err| / bound, worst relative L2 / yardstick over the engine's cases; every case prints its own line.)"""
-import os
-
 import numpy as np
 import pytest
 import torch
 
 from oracle import conv_cases as CC
 from oracle import conv_ref as R
+from _conv_checks import check, reference, reference_of
+from _fp64 import _ratio
+from _guarded import HWG_ERR_ARG, HWG_ERR_WORKSPACE, carve, put, same_bits
 
 pytestmark = pytest.mark.gpu
-
-YARDSTICK_FACTOR = 10.0      # the project's constant (tests/test_seq_loss_fp64_gpu.py)
-GUARD = 64                   # floats of canary before, between and after the carved buffers
-CANARY = -7.0e33
-HWG_ERR_ARG, HWG_ERR_WORKSPACE = -1, -3
-WINO_C = {"wino": 2 + 4 + 4, "s2": 2 + 2 + 4}
-
-
-def _cpu_threads():
-    torch.set_num_threads(min(16, os.cpu_count() or 1))
-
-
-def _rel(got, want):
-    d = got.detach().cpu().double() - want.double()
-    if not bool(torch.isfinite(d).all()):
-        return float("inf")
-    return float(d.norm()) / max(float(want.double().norm()), 1e-300)
-
-
-def _ratio(got, want, bound):
-    """worst |err| / bound over the elements (an element with a bound of 0 must be exact)"""
-    err = (got.detach().cpu().double() - want).abs()
-    if not bool(torch.isfinite(err).all()):
-        return float("inf")
-    if err.numel() == 0:
-        return 0.0
-    r = torch.where(bound > 0, err / bound.clamp_min(1e-300), torch.where(err > 0, torch.full_like(err, float("inf")), torch.zeros_like(err)))
-    return float(r.max())
-
-
-def same_bits(a, b):
-    a, b = a.detach().cpu().contiguous(), b.detach().cpu().contiguous()
-    return a.shape == b.shape and torch.equal(a.view(torch.int32), b.view(torch.int32))
-
-
-# ---- references (also used, without a GPU, by tests/test_conv_ref_cpu.py: its seeded flaws are measured against these bounds) ---------------
-def extra_ops(c):
-    """c of the bound: rounded operations past the contraction on the longest path to an output element"""
-    return WINO_C.get(c["engine"], 0) + int(c["bias"]) + int(c["acc"]) + CC.pieces(c) - 1
-
-
-def restate(c, x, w, b, y0, absolute=False):
-    """the engine's own algorithm in the dtype of the operands"""
-    fn = {"wino": R.wino_conv, "s2": R.wino_s2_conv}.get(c["engine"], R.conv_direct)
-    return fn(x, w, CC.geom(c), b, y0, absolute=absolute)
-
-
-def reference_of(c, x, w, b, y0, terms=None):
-    """(fp64 direct form, relative L2 of the fp32 restatement of the engine's algorithm against it, per-element bound)"""
-    _cpu_threads()
-    d = lambda t: None if t is None else t.double()
-    ref = R.conv_direct(d(x), d(w), CC.geom(c), d(b), d(y0))
-    yard = _rel(restate(c, x, w, b, y0), ref)
-    A = restate(c, d(x), d(w), d(b), d(y0), absolute=True)
-    return ref, yard, R.sum_bound((CC.contraction(c) if terms is None else terms) + extra_ops(c), A)
-
-
-_REF = {}
-
-
-def reference(c):
-    if c["name"] not in _REF:
-        _REF[c["name"]] = reference_of(c, *CC.inputs(c))
-    return _REF[c["name"]]
-
-
-# ---- buffers with canaries -------------------------------------------------------------------------------------------------------------------
-def carve(dev, *numels):
-    """-> ([flat float32 views of one allocation, 256-byte aligned, GUARD floats of canary around each], intact()): a 16-byte store past the
-    end of a buffer, or before its start, lands in a canary (the helper of tests/test_resample_glue_fp64_gpu.py)"""
-    offs, pos = [], GUARD
-    for n in numels:
-        offs.append(pos)
-        pos += (n + 63) // 64 * 64 + GUARD
-    buf = torch.full((pos,), CANARY, dtype=torch.float32, device=dev)
-    views = [buf[o:o + n] for o, n in zip(offs, numels)]
-
-    def intact():
-        live = torch.zeros(pos, dtype=torch.bool, device=dev)
-        for o, n in zip(offs, numels):
-            live[o:o + n] = True
-        return bool((buf[~live] == CANARY).all())
-    return views, intact
-
-
-def put(view, t):
-    view.copy_(t.reshape(-1).to(view.device))
-    return view
 
 
 class Run:
@@ -227,18 +141,6 @@ def run_case(c, dev, x, w, b, y0):
             assert same_bits(r.y, want_y), "%s: the refused call wrote to y" % name
         assert r.intact() and r.untouched(), "%s: canaries / inputs after the repeated calls" % name
     return y1
-
-
-def check(c, y, ref, yard, bound, tag=""):
-    rel = _rel(y, ref)
-    ratio = _ratio(y, ref, bound)
-    print("\nconv_fp64 %-34s %-5s rel %.3e yard %.3e (x%.2f) e/b %.3g%s" % (c["name"], c["engine"], rel, yard, rel / yard if yard > 0 else 0.0, ratio, tag))
-    bad = []
-    if not ratio <= 1.0:
-        bad.append("|err| is %.3g x the derived bound" % ratio)
-    if yard > 0 and rel > YARDSTICK_FACTOR * yard:
-        bad.append("rel L2 %.3e is %.1f x the fp32 yardstick %.3e" % (rel, rel / yard, yard))
-    assert not bad, "%s: %s" % (c["name"], "; ".join(bad))
 
 
 @pytest.mark.parametrize("c", CC.RUN_CASES, ids=[c["name"] for c in CC.RUN_CASES])

@@ -4,9 +4,6 @@ tests/test_conv_fp64_gpu.py is sound for the reference alone), the bookkeeping o
 dispatch code is reached, impulse footprints are disjoint, the library's planners - which need no GPU - give the schedule, split and
 workspace every case claims) and the sensitivity of the tables: plausible kernel flaws, seeded into copies of the restatements that live in
 this file only, each move some case past the bound the GPU file holds it to by SENSITIVITY_FACTOR or more, or flip an exact comparison."""
-import importlib.util
-import os
-
 import numpy as np
 import pytest
 import torch
@@ -14,21 +11,14 @@ import torch.nn.functional as F
 
 from oracle import conv_cases as CC
 from oracle import conv_ref as R
+import _conv_checks as G  # the references and bounds the GPU file holds the device to
+from _fp64 import _ratio, cpu_threads
 
 SENSITIVITY_FACTOR = 10.0
 TOL = 1e-10
 
 
-def _gpu_module():
-    """the GPU test's references and bounds (importing it needs no GPU)"""
-    spec = importlib.util.spec_from_file_location("conv_fp64_gpu_refs", os.path.join(os.path.dirname(os.path.abspath(__file__)), "test_conv_fp64_gpu.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-G = _gpu_module()
-G._cpu_threads()
+cpu_threads()
 
 
 def _nchw(t):
@@ -67,7 +57,7 @@ def test_restatements_match_torch_and_bound_their_own_fp32_error(engine):
         if engine in ("wino", "s2"):
             _close(G.restate(c, d(x), d(w), d(b), d(y0)), ref, c["name"] + " Winograd form")
         # A (A_w) dominates the fp32 restatement's own error: the bound is sound for the reference alone
-        r = G._ratio(G.restate(c, x, w, b, y0), ref, bound)
+        r = _ratio(G.restate(c, x, w, b, y0), ref, bound)
         assert r <= 1.0, "%s: the fp32 restatement is %.3g x the bound off" % (c["name"], r)
         assert yard > 0
 
@@ -321,8 +311,8 @@ def test_every_seeded_flaw_moves_a_case_past_its_bound():
         x, w, b, y0 = (None if t is None else t.double() for t in CC.inputs(c))
         ref, yard, bound = G.reference(c)
         fn = flawed_wino if c["engine"] == "wino" else flawed_direct
-        with_flaw = G._ratio(fn(c, x, w, b, y0, flaw), ref, bound)
-        without = G._ratio(G.restate(c, x, w, b, y0), ref, bound)
+        with_flaw = _ratio(fn(c, x, w, b, y0, flaw), ref, bound)
+        without = _ratio(G.restate(c, x, w, b, y0), ref, bound)
         print("%-44s moves %-28s to %.3g x the bound (without the flaw: %.3g)" % (flaw, name, with_flaw, without))
         assert without <= 1.0, "%s: the copy without the flaw is off the reference" % flaw
         assert with_flaw >= SENSITIVITY_FACTOR, "%s: moves its case by only %.3g x the bound" % (flaw, with_flaw)

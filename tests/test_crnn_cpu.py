@@ -1,7 +1,6 @@
 """CPU checks of the CRNN recogniser's references and plumbing (no GPU): the numpy fp64 LSTM against torch.nn.LSTM in fp64, the project's
 fp64 CRNN restatement against the reference's recorded float32 logits, the new CRNN's state-dict keys and shapes, and the `hwr` config
 parsing of HWWithStyle."""
-import glob
 import os
 
 import numpy as np
@@ -10,9 +9,7 @@ import torch
 
 import _crnn_ref
 import _lstm_ref
-
-GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "crnn")
-GOLDENS = sorted(glob.glob(os.path.join(GOLD, "*.npz")))
+from _crnn_golden import GOLD, GOLDENS, golden_case, seeded_sd
 
 
 def _rel(a, b):
@@ -55,29 +52,6 @@ def test_lstm_ref_mask_is_applied_between_the_layers():
     want, _ = _lstm_ref.forward(y1 * mask, [p[1]])        # layer 1 alone on the masked output of layer 0
     got, _ = _lstm_ref.forward(x, p, [mask])
     assert np.array_equal(got, want)
-
-
-def golden_case(path):
-    z = np.load(path)
-    return dict(pixels=z["pixels"], logits=z["logits"], norm=str(z["norm"]), pad=(str(z["pad"]) or False), nclass=int(z["nclass"]), wseed=int(z["wseed"]),
-                keys=[str(k) for k in z["keys"]], shapes=[tuple(int(d) for d in str(s).split(",") if d) for s in z["shapes"]], max_pre=float(z["max_pre"]))
-
-
-def seeded_sd(keys, shapes, seed):
-    """oracle.torch_ref.seeded_state_dict needs a module only for its key names and shapes: a stand-in built from the golden's recorded list,
-    so that this works before (and independently of) the class under test"""
-    from oracle import torch_ref
-
-    class Stand:
-        def __init__(self):
-            self.sd = {k: (torch.zeros(s, dtype=torch.int64) if k.endswith("num_batches_tracked") else torch.zeros(s)) for k, s in zip(keys, shapes)}
-
-        def named_parameters(self):
-            return [(k, v) for k, v in self.sd.items() if not k.endswith(("running_mean", "running_var", "num_batches_tracked"))]
-
-        def state_dict(self):
-            return self.sd
-    return torch_ref.seeded_state_dict(Stand(), seed)
 
 
 def test_goldens_are_recorded():

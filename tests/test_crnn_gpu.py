@@ -16,7 +16,7 @@ import torch.nn.functional as F
 
 import _crnn_ref
 from _gpu_tidy import leave_nothing_behind, scrub  # noqa: F401  (leave_nothing_behind: module-scoped, autouse)
-from test_crnn_cpu import GOLDENS, golden_case, seeded_sd
+from _crnn_golden import GOLDENS, golden_case, seeded_sd
 
 pytestmark = pytest.mark.gpu
 EPS = 2.0 ** -24

@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 import torch
 
-from test_reference_checkpoint_cpu import unpack
+from _reference_checkpoint import unpack
 
 pytestmark = pytest.mark.gpu
 

@@ -269,7 +269,7 @@ def test_trainer_with_the_store_equals_the_trainer_without_it(cuda, dirs, tmp_pa
 
 def test_synth_trainer_runs_behind_the_store(cuda, dirs, tmp_path):
     """HWRWithSynthTrainer with the store on: the real rows arrive augmented from the store and pass the mixed batch's augmentation unchanged"""
-    from test_reference_checkpoint_cpu import unpack
+    from _reference_checkpoint import unpack
 
     from handwriting_line_generation_amd import rng
     from handwriting_line_generation_amd.logger import load_checkpoint

@@ -5,27 +5,15 @@ restatement (every k of 0 .. H-1 exactly once, per gate block); the bookkeeping 
 reached, the impulse inputs meet every k mod 64 class in every gate block); and the sensitivity of the table: plausible kernel flaws, seeded
 into a tile-by-tile copy of the restatement that lives in this file only, each move some case past a condition the GPU file holds it to by
 SENSITIVITY_FACTOR or more, or flip an exact comparison (a NaN the call left behind, a canary, a zero row, an impulse)."""
-import importlib.util
-import os
-
 import numpy as np
 import pytest
 
+import _lstm_checks as G  # the conditions the GPU file holds the device to
 from oracle import lstm_cases as LC
+from _fp64 import cpu_threads
 
 SENSITIVITY_FACTOR = 10.0
-
-
-def _gpu_module():
-    """the GPU test's conditions (importing it needs no GPU)"""
-    spec = importlib.util.spec_from_file_location("lstm_fp64_gpu_refs", os.path.join(os.path.dirname(os.path.abspath(__file__)), "test_lstm_fp64_gpu.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-G = _gpu_module()
-G.F._cpu_threads()
+cpu_threads()
 
 
 # ---- the restatement against fp64, within the GPU file's bounds ----------------------------------------------------------------------------------

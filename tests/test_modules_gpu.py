@@ -12,7 +12,7 @@ import pytest
 import torch
 
 from oracle import cases, torch_ref
-from test_oracle_golden import GOLD, GRAD_INPUTS, ORACLE_FWD, PERTURB, _oracle_grads64, product_module, rel
+from _oracle_modules import GOLD, GRAD_INPUTS, ORACLE_FWD, PERTURB, _oracle_grads64, product_module, rel
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4

@@ -16,7 +16,7 @@ import torch
 
 import _eval_pictures_ref as ref
 from _gpu_tidy import leave_nothing_behind  # noqa: F401
-from test_reference_checkpoint_cpu import unpack
+from _reference_checkpoint import unpack
 
 pytestmark = pytest.mark.gpu
 

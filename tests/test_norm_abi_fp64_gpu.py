@@ -1,10 +1,10 @@
 """GPU: the entries of csrc/norm_act.hip - hwg_norm_fwd / _bwd, hwg_norm_frozen_fwd, hwg_adain_fwd / _fwd_rng / _bwd, hwg_bias_act_fwd / _bwd -
 and hwg_colsum, called at the C ABI through L.query (return codes visible, never through ops but for the bit comparisons named below) on
 guarded buffers, against the fp64 restatements of oracle/norm_ref.py. Case tables and the regimes they cover: oracle/abi_cases.py, checked on
-the CPU by tests/test_abi_cases_cpu.py. The buffers are those of tests/test_conv_fp64_gpu.py, loaded from there; the bounds are the BOUNDS of
-tests/test_norm_act_fp64_gpu.py, imported: the same kernels and the same arithmetic. The library's default tuning only.
+the CPU by tests/test_abi_cases_cpu.py. The buffers and the protocol are those of tests/_guarded.py; the bounds are the BOUNDS of
+tests/_norm_act_checks.py, which tests/test_norm_act_fp64_gpu.py holds the same kernels to: the same arithmetic. The library's default tuning only.
 
-The protocol, for every entry (class Guarded, protocol()): every operand, every output and the workspace are carved out of ONE allocation with
+The protocol, for every entry (Guarded and protocol() of tests/_guarded.py): every operand, every output and the workspace are carved out of ONE allocation with
 64-float canaries before, between and after them. The workspace has exactly the bytes the entry's query returns (a multiple of 4). Before
 the call every output and the workspace are filled with NaN (an output the entry adds to: with its pre-filled value). After the call: return
 code 0, canaries intact, every input bit-identical, every output the call does not own unchanged, every documented output finite. A second
@@ -35,186 +35,17 @@ divided by its bound; every case prints its own line, kept in profiles/norm_seq_
                                 not added: exact. Bits of ops.colsum.
   refusals                      C % 4 != 0 and C > 1024 (every norm entry), groups not dividing C (hwg_norm_fwd, hwg_norm_bwd), BN with
                                 affine_per_sample: HWG_ERR_ARG before any launch, outputs still NaN, canaries intact."""
-import importlib.util
-import os
-import zlib
-
-import numpy as np
 import pytest
 import torch
 
 from oracle import abi_cases as AC
 from oracle import norm_ref as R
+from _fp64 import SECOND, U, _f32, _gen, _ratio, cpu_threads, report
 from _gpu_tidy import leave_nothing_behind  # noqa: F401  (module-scoped, autouse)
+from _guarded import NAN, Guarded, bits_differ, protocol, refused, same_bits
+from _norm_act_checks import BOUNDS, EPS, MAX_FLIPS, MOMENTUM, _gate_hint, nhwc, norm_inputs
 
 pytestmark = pytest.mark.gpu
-
-
-def _load(fname):
-    """another test file's helpers (importing it needs no GPU)"""
-    spec = importlib.util.spec_from_file_location(fname[:-3] + "_shared", os.path.join(os.path.dirname(os.path.abspath(__file__)), fname))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-F = _load("test_conv_fp64_gpu.py")
-NA = _load("test_norm_act_fp64_gpu.py")
-carve, put, same_bits, HWG_ERR_ARG, HWG_ERR_WORKSPACE = F.carve, F.put, F.same_bits, F.HWG_ERR_ARG, F.HWG_ERR_WORKSPACE
-BOUNDS, EPS, MOMENTUM, MAX_FLIPS, _f32, _gate_hint = NA.BOUNDS, NA.EPS, NA.MOMENTUM, NA.MAX_FLIPS, NA._f32, NA._gate_hint
-U = 2.0 ** -24
-SECOND = 1 + 2.0 ** -16
-NAN = float("nan")
-
-
-# ---- guarded buffers and the protocol (also loaded by tests/test_seq_loss_abi_fp64_gpu.py) -------------------------------------------------------
-class Guarded:
-    """inputs {name: CPU tensor}, outputs {name: (shape, dtype) - filled with NaN bits before a call - or a CPU tensor - pre-filled with it}
-    and a workspace of exactly `ws_bytes`, all carved out of one allocation. 4- and 8-byte element types (and bytes, in multiples of 4)."""
-
-    def __init__(self, dev, inputs, outputs, ws_bytes=0):
-        from handwriting_line_generation_amd import _lib as L, ops
-        self.L, self.st, self.dev = L, ops._stream(), dev
-        assert ws_bytes % 4 == 0, "workspace of %d bytes: not a multiple of 4" % ws_bytes
-        self.need = int(ws_bytes)
-        self.ins, self.outs = list(inputs), list(outputs)
-        self.shape, self.dtype, self.init = {}, {}, {}
-        floats = []
-        for k, v in list(inputs.items()) + list(outputs.items()):
-            shape, dtype = (tuple(v.shape), v.dtype) if torch.is_tensor(v) else (tuple(v[0]), v[1])
-            nbytes = int(np.prod(shape, dtype=np.int64)) * torch.empty((), dtype=dtype).element_size()
-            assert nbytes % 4 == 0, (k, shape, dtype)
-            self.shape[k], self.dtype[k] = shape, dtype
-            self.init[k] = v.contiguous() if torch.is_tensor(v) else None
-            floats.append(nbytes // 4)
-        views, self.intact = carve(dev, *(floats + [self.need // 4]))
-        self.f = dict(zip(self.ins + self.outs, views))                 # flat float32 views
-        self.ws = views[-1] if self.need else None
-        for k in self.ins:
-            self.t(k).copy_(self.init[k])
-        self.reset()
-        torch.cuda.synchronize()
-        self.sent = {k: self.f[k].clone() for k in self.ins}
-
-    def t(self, k):
-        """the buffer in its own type and shape"""
-        return self.f[k].view(self.dtype[k]).view(self.shape[k])
-
-    def set_input(self, k, value):
-        self.t(k).copy_(value)
-        self.sent[k] = self.f[k].clone()
-
-    def reset(self, names=None):
-        for k in self.outs if names is None else names:
-            if self.init[k] is None:
-                self.f[k].fill_(NAN)
-            else:
-                self.t(k).copy_(self.init[k])
-
-    def ws_fill(self, value):
-        if self.ws is not None:
-            self.ws.fill_(value)
-
-    def untouched(self):
-        return all(same_bits(self.f[k], self.sent[k]) for k in self.ins)
-
-    def as_reset(self, names=None):
-        """the outputs that no longer hold what reset() put there"""
-        bad = []
-        for k in self.outs if names is None else names:
-            ok = bool(torch.isnan(self.f[k]).all()) if self.init[k] is None else same_bits(self.f[k], self.init[k].view(torch.float32).reshape(-1))
-            if not ok:
-                bad.append(k)
-        return bad
-
-    def get(self, k):
-        return self.t(k).detach().cpu().clone()
-
-
-def protocol(G, tag, call, mine=None, partly=(), poison_ws=True, sized=True):
-    """the protocol of the module docstring around one entry: call(ws, ws_bytes) -> return code. `mine`: the outputs the entry owns (all of
-    them by default), `partly`: those of them it need not fill. poison_ws = False: the workspace carries an earlier call's state (CTC backward)
-    -> {name: CPU tensor} of the first call"""
-    L = G.L
-    mine = list(G.outs) if mine is None else list(mine)
-    others = [k for k in G.outs if k not in mine]
-
-    def run(ws, n):
-        rc = call(ws, n)
-        torch.cuda.synchronize()
-        return rc
-
-    kept = {k: G.f[k].clone() for k in others}
-    G.reset(mine)
-    if poison_ws:
-        G.ws_fill(NAN)
-    rc = run(G.ws, G.need)
-    assert rc == 0, "%s returned %d: %s" % (tag, rc, L.last_error())
-    assert G.intact(), "%s: a canary next to a buffer was overwritten" % tag
-    assert G.untouched(), "%s: an input changed" % tag
-    assert all(same_bits(G.f[k], kept[k]) for k in others), "%s wrote to a buffer it does not own" % tag
-    first = {k: G.f[k].clone() for k in mine}
-    for k in mine:
-        if k not in partly and G.dtype[k] == torch.float32:
-            n = int((~torch.isfinite(first[k])).sum())
-            assert n == 0, "%s: %d elements of %s are not finite (never written, or written from workspace contents)" % (tag, n, k)
-    out = {k: G.get(k) for k in mine}
-    G.reset(mine)
-    if poison_ws:
-        G.ws_fill(0.0)
-    assert run(G.ws, G.need) == 0, tag
-    differ = [k for k in mine if not same_bits(G.f[k], first[k])]
-    assert not differ, "%s: the second call (workspace zero-filled) gives other bits in %s" % (tag, differ)
-    assert G.intact() and G.untouched(), "%s: canaries / inputs after the second call" % tag
-    if G.need and sized:
-        for what, ws, n in (("one byte of workspace too few", G.ws, G.need - 1), ("no workspace", None, G.need)):
-            G.reset(mine)
-            rc = run(ws, n)
-            assert rc == HWG_ERR_WORKSPACE, "%s with %s returned %d" % (tag, what, rc)
-            assert not G.as_reset(mine), "%s with %s wrote to %s" % (tag, what, G.as_reset(mine))
-            assert G.intact() and G.untouched(), "%s with %s: canaries / inputs" % (tag, what)
-    return out
-
-
-def refused(G, tag, call, code=HWG_ERR_ARG):
-    """a call the host code turns down before any launch: its code, nothing written"""
-    G.reset()
-    rc = call()
-    torch.cuda.synchronize()
-    assert rc == code, "%s returned %d" % (tag, rc)
-    assert not G.as_reset(), "%s wrote to %s" % (tag, G.as_reset())
-    assert G.intact() and G.untouched(), tag
-
-
-def ratios(got, want, bound, size=None):
-    """(relative L2 / its bound, max|err| / max|ref| / its bound); inf for a non-finite output. `size`: the float64 tensor whose size the
-    error is measured against instead of want's (where want is the small difference of large terms)"""
-    got = got.detach().cpu().double().reshape(want.shape)
-    if not bool(torch.isfinite(got).all()):
-        return float("inf"), float("inf")
-    d = got - want
-    size = want if size is None else size
-    return (float(d.norm()) / max(float(size.norm()), 1e-300) / bound[0], float(d.abs().max()) / max(float(size.abs().max()), 1e-300) / bound[1])
-
-
-def report(entry, shape, ws_bytes, checks):
-    """checks: [(name, got, want float64, bound[, size])] -> prints the case's line, returns what is over its bound"""
-    parts, bad = [], []
-    for name, got, want, bound, *size in checks:
-        r = ratios(got, want, bound, *size)
-        parts.append("%s %.2f/%.2f" % (name, r[0], r[1]))
-        if not (r[0] <= 1.0 and r[1] <= 1.0):
-            bad.append("%s: relative L2 %.3g x, max/max %.3g x its bound (%.1e, %.1e)" % (name, r[0], r[1], bound[0], bound[1]))
-    print("\nabi %-22s %-34s ws %-9d e/b %s" % (entry, shape, ws_bytes, "  ".join(parts) if parts else "-"))
-    return bad
-
-
-def bits_differ(pairs):
-    return [name for name, a, b in pairs if not same_bits(a.reshape(-1), b.reshape(-1))]
-
-
-def _gen(name):
-    return torch.Generator().manual_seed(zlib.crc32(name.encode()))
 
 
 def nchw(t, N, HW, C):
@@ -222,40 +53,7 @@ def nchw(t, N, HW, C):
     return t.detach().cpu().double().reshape(N, 1, HW, C).permute(0, 3, 1, 2).contiguous()
 
 
-def nhwc(t):
-    """NCHW [N, C, 1, HW] as the kernels' [N, 1, HW, C]"""
-    return t.permute(0, 2, 3, 1).contiguous()
-
-
 # ---- normalisation ---------------------------------------------------------------------------------------------------------------------------
-FEW_PIXELS = 16
-
-
-def norm_inputs(c, per_sample=False):
-    """x = 2 randn + 0.5, the inputs of tests/test_norm_act_fp64_gpu.py. With fewer than FEW_PIXELS pixels per channel an InstanceNorm
-    statistic is formed from 3 or 5 values, and among 2048 such groups of 2 randn + 0.5 the smallest sample variance is 1e-3 of the group's
-    mean square: there the kernels' variance E[x^2] - E[x]^2 from fp32 lane sums keeps four digits (measured at C 1024, HW 3: y 5e-5, dx 2e-3
-    of the tensor's maximum - the arithmetic whose cost the "offset16" family of that file measures at mean = 16 sigma), and fp64 itself moves
-    by 1e-6 when x moves by an ulp. That is the conditioning of the drawn problem, not the one-chunk regime these shapes are here for: below
-    FEW_PIXELS every (n, c) row is standardised to a sample deviation s in [0.5, 2] and a mean of s / 4, whatever the mode pools."""
-    N, HW, C = c["N"], c["HW"], c["C"]
-    g = _gen(c["name"])
-    t = dict(x=torch.randn(N, C, 1, HW, generator=g) * 2 + 0.5)
-    if HW < FEW_PIXELS:
-        z = t["x"].double()
-        s = torch.rand(N, C, 1, 1, generator=g).double() * 1.5 + 0.5
-        t["x"] = (((z - z.mean(3, keepdim=True)) / z.std(3, unbiased=False, keepdim=True) + 0.25) * s).float()
-    ash = (N, C) if per_sample else (C,)
-    t["gamma"] = torch.rand(ash, generator=g) + 0.5
-    t["beta"] = torch.randn(ash, generator=g)
-    t["mask"] = ((torch.rand(N, C, generator=g) > 0.3).float() / 0.7) if c["mask"] else None
-    t["gy"] = torch.randn(N, C, 1, HW, generator=g)
-    t["rm0"] = torch.randn(C, generator=g) * 0.3 + 0.2
-    t["rv0"] = torch.rand(C, generator=g) + 0.5
-    scale = (N * HW) ** 0.5
-    t["dgamma0"] = torch.randn(ash, generator=g) * scale
-    t["dbeta0"] = torch.randn(ash, generator=g) * scale
-    return t
 
 
 def norm_forward(dev, c, t, per_sample=0, tag=None, run=protocol):
@@ -307,7 +105,7 @@ def norm_backward(dev, c, t, fwd, per_sample=0, accumulate=0, tag=None):
 
 def norm_reference(c, t, y_kernel, per_sample=False):
     """fp64: y, dx, dgamma, dbeta (and the running statistics after one update), gates near 0 taken from the kernel's forward output"""
-    NA._cpu_threads()
+    cpu_threads()
     x64, g64, b64 = (t[k].double().requires_grad_(True) for k in ("x", "gamma", "beta"))
     m64 = t["mask"].double() if t["mask"] is not None else None
     z = R.norm_pre(x64, c["mode"], c["groups"], g64, b64, m64, _f32(EPS))
@@ -460,7 +258,7 @@ def test_generator_epilogue_entries_on_guarded_buffers_vs_fp64(cuda, case):
         "hwg_adain_bwd", k["dy"], k["u"], k["noise"], scale, slope, k["gamma"], k["mean"], k["rstd"], k["dx"], k["dgamma"], k["dbeta"], k["dnw"], k["dbias"], 1,
         N, HW, C, ws, n, G3.st))
     # fp64, the leaky relu's gates near 0 from the kernel's u
-    NA._cpu_threads()
+    cpu_threads()
     nz = noise.reshape(N, 1, HW, C).permute(0, 3, 1, 2).double()
     x64, nw64, g64, b64 = (t[q].double().requires_grad_(True) for q in ("x", "nw", "gamma", "beta"))
     pre = R.adain_pre(x64, nz, nw64, _f32(scale))
@@ -589,7 +387,7 @@ def test_colsum_on_guarded_buffers_vs_fp64(cuda, rows, C, accumulate):
     got = protocol(G, "hwg_colsum %dx%d" % (rows, C), lambda ws, n: L.query("hwg_colsum", f["x"], rows, C, f["out"], accumulate, ws, n, G.st))["out"]
     want = x.double().sum(0) + (out0.double() if accumulate else 0.0)
     bound = (rows - 1 + accumulate) * U * (x.double().abs().sum(0) + (out0.double().abs() if accumulate else 0.0)) * SECOND
-    worst = F._ratio(got, want, bound)
+    worst = _ratio(got, want, bound)
     print("\nabi %-22s %-34s ws %-9d e/b out %.2f" % ("hwg_colsum", "rows%d C%d acc%d" % (rows, C, accumulate), need, worst))
     o = ops.colsum(x.to(cuda), out=out0.to(cuda) if accumulate else None, accumulate=bool(accumulate))
     assert same_bits(got, o), "hwg_colsum %dx%d: differs from the bits of ops.colsum" % (rows, C)

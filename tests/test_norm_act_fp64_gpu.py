@@ -1,59 +1,23 @@
 """GPU: the normalisation / activation kernels (csrc/norm_act.hip; the tanh pass of csrc/spectral_loss.hip) against the fp64 CPU restatements
 of oracle/norm_ref.py, at the training step's geometries and at every chunk, lane and statistics regime of the kernels (case tables and the
-regimes they cover: oracle/norm_cases.py, checked on the CPU by tests/test_norm_act_ref_cpu.py). The library's default path only.
+regimes they cover: oracle/norm_cases.py, checked on the CPU by tests/test_norm_act_ref_cpu.py). The library's default path only. The bounds (BOUNDS, shared with
+tests/test_norm_abi_fp64_gpu.py) are those of tests/_norm_act_checks.py.
 
 Every output - y, dx, dgamma, dbeta, d(noise weight), running_mean, running_var - is compared by its relative L2 error and by
 max|err| / max|ref|; one line per case is printed. relu / leaky relu gates whose fp64 pre-activation lies within 1e-6 of its largest magnitude
 take the kernel's own forward output in the fp64 backward (the kernel recomputes the gate in fp32 and may fall on the other side of 0); the
 number of those gates that really differ from fp64's sign is asserted to be a handful."""
-import os
-import zlib
-
 import pytest
 import torch
 
 from oracle import norm_cases as NC
 from oracle import norm_ref as R
+from _fp64 import _f32, _gen, cpu_threads
+from _norm_act_checks import BOUNDS, EPS, MAX_FLIPS, MOMENTUM, _gate_hint, nhwc
 
 pytestmark = pytest.mark.gpu
 
-# (relative L2, max|err| / max|ref|) per family: 4x the worst case measured on an MI355X (in brackets), rounded down.
-# An off-by-one count, a dropped chunk, the biased running variance or a lost pre-filled gradient move some case by 1e-3 or more.
-BOUNDS = {
-    "norm_fwd": (2.2e-7, 1.7e-6),         # [5.7e-8, 4.3e-7]  GN / BN / IN forward (tanh: tanhf's ulps)
-    "norm_grad": (4.3e-7, 6.7e-7),        # [1.1e-7, 1.7e-7]  dx, dgamma, dbeta
-    "norm_stats": (2.5e-7, 4.7e-7),       # [7.1e-8, 1.3e-7]  running_mean, running_var after two updates
-    "offset16": (2.7e-6, 4.9e-6),         # [6.9e-7, 1.2e-6]  mean 16 sigma, forward and gradients (fp32 lane sums of x^2)
-    "adain_fwd": (2.0e-7, 5.9e-7),        # [5.2e-8, 1.5e-7]
-    "adain_grad": (6.0e-7, 1.0e-6),       # [1.5e-7, 2.6e-7]  dx, dgamma, dbeta, d(noise weight)
-    "frozen": (2.3e-7, 1.0e-6),           # [5.9e-8, 2.7e-7]
-    "bias_act_fwd": (1.4e-7, 2.7e-7),     # [3.7e-8, 6.8e-8]
-    "bias_act_grad": (4.3e-7, 4.5e-7),    # [1.1e-7, 1.1e-7]  dx, dbias
-    "tanh_fwd": (9.4e-8, 3.2e-7),         # [2.4e-8, 8.1e-8]
-    "tanh_grad": (2.6e-7, 3.2e-7),        # [6.6e-8, 8.1e-8]
-}
-NEAR = 1e-6          # |z64| < NEAR * max|z64|: the gate comes from the kernel's forward output
-MAX_FLIPS = 8        # gates where that differs from the sign of the fp64 pre-activation
-EPS, MOMENTUM = 1e-5, 0.1
-
 _REF = {}
-
-
-def _f32(v):
-    """a Python float as the kernels receive it"""
-    return float(torch.tensor(v, dtype=torch.float32))
-
-
-def _cpu_threads():
-    torch.set_num_threads(min(16, os.cpu_count() or 1))
-
-
-def nhwc(t):
-    return t.permute(0, 2, 3, 1).contiguous()
-
-
-def _gen(name):
-    return torch.Generator().manual_seed(zlib.crc32(name.encode()))
 
 
 def _errs(got, want):
@@ -74,16 +38,6 @@ def _check(label, outs, family, note=""):
             bad.append("%s: rel L2 %.3e (bound %.1e), max/max %.3e (bound %.1e)" % (name, rel, rel_b, mx, max_b))
     print("\n%-34s [%s] rel L2 / max-max vs fp64: %s%s" % (label, family, "  ".join(parts), note))
     assert not bad, "%s vs fp64: %s" % (label, "; ".join(bad))
-
-
-def _gate_hint(z, y_kernel, act):
-    """(hint for R.act_ref, gates taken from the kernel, of those where the kernel's sign differs from fp64's) - relu / leaky relu only"""
-    if act not in (R.ACT_RELU, R.ACT_LRELU):
-        return None, 0, 0
-    zd = z.detach()
-    near = (zd.abs() < NEAR * float(zd.abs().max())) & (zd != 0)
-    positive = y_kernel > 0
-    return (near, positive), int(near.sum()), int((near & (positive != (zd > 0))).sum())
 
 
 def _gates(ref):
@@ -126,7 +80,7 @@ def _norm_reference(case, x, gamma, beta, mask, gy, rm0, rv0, y_kernel):
     name, mode, N, H, W, C, groups, act, slope, use_mask, inputs, path = case
     if name in _REF:
         return _REF[name]
-    _cpu_threads()
+    cpu_threads()
     affine = path is not None
     x64 = x.double().requires_grad_(True)
     g64 = gamma.double().requires_grad_(True) if affine else None
@@ -222,7 +176,7 @@ def test_generator_epilogue_vs_fp64(cuda, case, defer):
             y = ops.adain_epilogue(xg, vn, nwg, gg, bg, scale, 0.2, EPS)
             nz = R.to_nchw(vn.materialise(cuda)).float()
         if name not in _REF:
-            _cpu_threads()
+            cpu_threads()
             _REF[name] = {"y": R.adain(x.double(), nz.double(), nw.double(), gamma.double(), beta.double(), _f32(scale), _f32(0.2), _f32(EPS))}
         _check(name + " fwd", [("y", R.to_nchw(y), _REF[name]["y"])], "adain_fwd")
         return
@@ -230,7 +184,7 @@ def test_generator_epilogue_vs_fp64(cuda, case, defer):
     y = ops.adain_epilogue(xg, nhwc(nz).to(cuda), nwg, gg, bg, scale, 0.2, EPS)
     u_kernel = R.to_nchw(y.grad_fn.saved_tensors[0])       # the kernel's lrelu output: its backward gates on u > 0
     if name not in _REF:
-        _cpu_threads()
+        cpu_threads()
         x64, nw64, g64, b64 = (t.double().requires_grad_(True) for t in (x, nw, gamma, beta))
         t = R.adain_pre(x64, nz.double(), nw64, _f32(scale))
         hint, near, flips = _gate_hint(t, u_kernel, R.ACT_LRELU)

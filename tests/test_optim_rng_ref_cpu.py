@@ -11,21 +11,12 @@ import torch
 
 from oracle import optim_cases as OC
 from oracle import optim_ref as R
+import _optim_rng_checks as G  # the bounds the GPU file holds each family to
+from _fp64 import _f32
 
 SENSITIVITY_FACTOR = 10.0
 
 
-def _gpu_module():
-    """the GPU test's module, for the bounds it holds each family to (importing it needs no GPU)"""
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("optim_rng_fp64_gpu_bounds", os.path.join(os.path.dirname(os.path.abspath(__file__)), "test_optim_rng_fp64_gpu.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-G = _gpu_module()
-_f32 = G._f32
 # a flaw in the normals has to show against the measured bound; until one is measured, against the derived one the GPU test uses meanwhile
 RANDN_BOUND = G.RANDN_ABS if G.RANDN_ABS is not None else G.RANDN_DERIVED
 

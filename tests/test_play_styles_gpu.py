@@ -22,8 +22,8 @@ import pytest
 import torch
 
 import _play_styles_ref as ref
-from test_error_rates_gpu import _child, program  # noqa: F401  (the fabricated IAM directory + checkpoint fixture of the get_styles.py test)
-from test_writer_id_gpu import gaussian_case, quarter_case
+from _get_styles_program import _child, program  # noqa: F401  (the fabricated IAM directory + checkpoint fixture of the get_styles.py test)
+from _writer_id_cases import gaussian_case, quarter_case
 
 pytestmark = pytest.mark.gpu
 

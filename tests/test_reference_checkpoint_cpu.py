@@ -1,20 +1,11 @@
 """CPU: checkpoints written by the REFERENCE's `_save_checkpoint` (tests/golden/ref_ckpt_*.pth.xz, made by tools/gen_golden_checkpoint.py) unpickle
 here - the pickled `logger.logger.Logger` resolves through the shim - and carry the layout `_resume_checkpoint` expects."""
 import json
-import lzma
 import os
 
 import pytest
-import torch
 
-GOLD = os.path.join(os.path.dirname(__file__), "golden")
-
-
-def unpack(name, tmp_path):
-    dst = os.path.join(str(tmp_path), "ref_ckpt_%s.pth" % name)
-    with open(dst, "wb") as f:
-        f.write(lzma.decompress(open(os.path.join(GOLD, "ref_ckpt_%s.pth.xz" % name), "rb").read()))
-    return dst
+from _reference_checkpoint import GOLD, unpack
 
 
 @pytest.mark.parametrize("name,arch,iteration", [("gan", "HWWithStyle", 25000), ("hwr", "HWWithStyle", 100000), ("auto", "Autoencoder", 60000)])

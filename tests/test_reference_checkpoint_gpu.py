@@ -11,7 +11,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import torch_ref
-from test_reference_checkpoint_cpu import GOLD, unpack
+from _reference_checkpoint import GOLD, unpack
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4

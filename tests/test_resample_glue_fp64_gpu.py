@@ -2,7 +2,8 @@
 channel copies, pad_channels, reduce_rows, one-hot, permute4, the FusedUpsample weight, col2im_taps) and the glue kernels at the end of
 csrc/spectral_loss.hip (axpby, mul, channel_affine, weighted_sum, style_mix) against the restatements of oracle/resample_ref.py, at every
 regime of the kernels (case tables and the regimes they cover: oracle/resample_cases.py; the restatements, the tables and their sensitivity
-to seeded flaws are checked on the CPU by tests/test_resample_glue_ref_cpu.py). The library's default path only. The entry points are
+to seeded flaws are checked on the CPU by tests/test_resample_glue_ref_cpu.py; the references and their bounds:
+tests/_resample_glue_checks.py; the buffers: tests/_guarded.py). The library's default path only. The entry points are
 called through L.call on buffers carved out of one allocation with canaries before, between and after them; the ops.py wrappers that had no
 unit test run through autograd.
 
@@ -29,71 +30,20 @@ fp32 torch on the CPU against the same fp64 value) and the worst |err| / bound o
 (No errors measured on an MI355X stand in the last column yet: every case prints its own on the line it writes.)
 Every output that is a sum is also held to YARDSTICK_FACTOR times its yardstick in relative L2 (a yardstick of exactly zero: the derived
 bound alone)."""
-import os
-
 import numpy as np
 import pytest
 import torch
 
 from oracle import resample_cases as SC
 from oracle import resample_ref as R
+from _fp64 import YARDSTICK_FACTOR, _d, _f, _ratio, entry
+from _guarded import CANARY, carve, put
+from _resample_glue_checks import (_cached, col2im_reference, copy_values, fused_inputs, nhwc_reference, reduce_values, same,
+                                    sums_of)
 
 pytestmark = pytest.mark.gpu
 
 ULP = 2.0 ** -23
-YARDSTICK_FACTOR = 10.0      # the project's constant (tests/test_seq_loss_fp64_gpu.py)
-GUARD = 64                   # floats of canary before, between and after the carved buffers
-CANARY = -7.0e33
-
-
-def _cpu_threads():
-    torch.set_num_threads(min(16, os.cpu_count() or 1))
-
-
-def _d(t):
-    return t.double()
-
-
-def _f(t):
-    return t.float()
-
-
-def _a(t):
-    return t.double().abs()
-
-
-def _rel(got, want):
-    d = got.detach().cpu().double() - want.double()
-    if not bool(torch.isfinite(d).all()):
-        return float("inf")
-    return float(d.norm()) / max(float(want.double().norm()), 1e-300)
-
-
-def _ratio(got, want, bound):
-    """worst |err| / bound over the elements (an element with a bound of 0 must be exact)"""
-    err = (got.detach().cpu().double() - want).abs()
-    if not bool(torch.isfinite(err).all()):
-        return float("inf")
-    if err.numel() == 0:
-        return 0.0
-    r = torch.where(bound > 0, err / bound.clamp_min(1e-300), torch.where(err > 0, torch.full_like(err, float("inf")), torch.zeros_like(err)))
-    return float(r.max())
-
-
-def entry(ref, yard32=None, bound=None):
-    """one output that is a sum: the fp64 value, the yardstick (relative L2 of the fp32 CPU restatement, None: none), the bound"""
-    return (ref, None if yard32 is None else _rel(yard32, ref), bound)
-
-
-def same(got, want):
-    """torch.equal with the NaN positions compared apart; the dtype has to match (int32 indices)"""
-    got = got.detach().cpu()
-    if got.dtype != want.dtype or tuple(got.shape) != tuple(want.shape):
-        return False
-    if want.dtype.is_floating_point:
-        gn, wn = torch.isnan(got), torch.isnan(want)
-        return torch.equal(gn, wn) and torch.equal(got.masked_fill(gn, 0), want.masked_fill(wn, 0))
-    return torch.equal(got, want)
 
 
 def _check(label, outs, exact, sums, note=""):
@@ -130,136 +80,10 @@ def _check(label, outs, exact, sums, note=""):
     assert not bad, "%s: %s" % (label, "; ".join(bad))
 
 
-_REF = {}
-
-
-def _cached(key, fn):
-    if key not in _REF:
-        _cpu_threads()
-        _REF[key] = fn()
-    return _REF[key]
-
-
-def sums_of(fn, K):
-    """fn(cast) -> {name: value}; K: {name: terms}; -> {name: entry} with the bound from the same restatement on absolute values"""
-    ref, yard, absv = fn(_d), fn(_f), fn(_a)
-    return {k: entry(v, yard[k], R.sum_bound(K[k], absv[k])) for k, v in ref.items()}
-
-
-# ---- references (also used, without a GPU, by tests/test_resample_glue_ref_cpu.py: its seeded flaws are measured against these bounds) ------
-def nhwc_K(case):
-    name, op, shape, prm = case
-    if op == "avgpool":
-        return {"y": prm["k"][0] * prm["k"][1] + 1, "dx": 1}
-    if op in ("maxpool", "maxpool_relu"):
-        (kh, kw), (sh, sw), _ = prm["geom"]
-        return {"dx": -(-kh // sh) * -(-kw // sw)}
-    if op == "upsample":
-        return {"dx": prm["f"][0] * prm["f"][1]}
-    if op == "blur":
-        return {"y": 9, "dx": 9}
-    if op == "pad" and prm["pad"][4] == 1:
-        pt, pb, pl, pr = prm["pad"][:4]
-        return {"dx": (max(pt, pb) + 1) * (max(pl, pr) + 1)}
-    return {}
-
-
-def nhwc_sum_values(case, cast, M=R):
-    """the outputs of the case that are sums, in the dtype of `cast`"""
-    name, op, (N, H, W, C), prm = case
-    x, dy, mask = SC.nhwc_inputs(case)
-    K = nhwc_K(case)
-    if op == "avgpool":
-        return {"y": M.avgpool_fwd(cast(x), *prm["k"]), "dx": M.avgpool_bwd(cast(dy), H, W, *prm["k"])}
-    if op in ("maxpool", "maxpool_relu") and K["dx"] > 1:
-        y, idx = M.maxpool_fwd(x, *prm["geom"], relu=op == "maxpool_relu")
-        return {"dx": M.maxpool_bwd(cast(dy), idx, H, W, y if op == "maxpool_relu" else None)}
-    if op == "upsample":
-        return {"dx": M.upsample_bwd(cast(dy), *prm["f"])}
-    if op == "blur":
-        return {"y": M.blur3(cast(x)), "dx": M.blur3(cast(dy))}
-    if op == "pad" and prm["pad"][4] == 1:
-        return {"dx": M.pad2d_bwd(cast(dy), H, W, *prm["pad"][:5])}
-    return {}
-
-
-def nhwc_exact_values(case, M=R):
-    """the outputs of the case that are held to torch.equal"""
-    name, op, (N, H, W, C), prm = case
-    x, dy, mask = SC.nhwc_inputs(case)
-    if op == "act_avgpool":
-        return {"y": M.act_avgpool_fwd_f32(x, mask, prm["act"], SC.SLOPE, *prm["k"]),
-                "dx": M.act_avgpool_bwd_f32(dy, x, mask, prm["act"], SC.SLOPE, *prm["k"])}
-    if op in ("maxpool", "maxpool_relu"):
-        y, idx = M.maxpool_fwd(x, *prm["geom"], relu=op == "maxpool_relu")
-        out = {"y": y, "idx": idx}
-        if nhwc_K(case)["dx"] == 1:
-            out["dx"] = M.maxpool_bwd(dy, idx, H, W, y if op == "maxpool_relu" else None)
-        return out
-    if op == "upsample":
-        return {"y": M.upsample_fwd(x, *prm["f"])}
-    if op == "pad":
-        out = {"y": M.pad2d_fwd(x, *prm["pad"])}
-        if prm["pad"][4] == 0:
-            out["dx"] = M.pad2d_bwd(dy, H, W, *prm["pad"][:5])
-        return out
-    return {}
-
-
-def nhwc_reference(case):
-    return _cached(("nhwc", case[0]), lambda: (nhwc_exact_values(case), sums_of(lambda cast: nhwc_sum_values(case, cast), nhwc_K(case))))
-
-
-def copy_values(case, cast, M=R):
-    name, rows, Cs, soff, Cd, doff, Cn, HW, bcast, acc = case
-    src, dst = SC.copy_inputs(case)
-    return {"dst": M.copy_channels(cast(src), soff, cast(dst), doff, Cn, HW, bcast, acc)}
-
-
-def reduce_values(case, cast, M=R):
-    name, N, HW, Cs, soff, Cn, acc = case
-    g = SC.gen("reduce_" + name)
-    src, prev = torch.randn(N * HW, Cs, generator=g), torch.randn(N, Cn, generator=g)
-    return {"out": M.reduce_rows(cast(src), soff, Cn, N, HW, cast(prev) if acc else None)}, src, prev
-
-
-def fused_inputs(AB):
-    g = SC.gen("fused_%dx%d" % AB)
-    return torch.randn(*AB, 3, 3, generator=g), torch.randn(*AB, 4, 4, generator=g), torch.randn(*AB, 3, 3, generator=g)
-
-
-def col2im_reference(case):
-    name, N, H, W, R_, S, ph, pw, dh, dw = case
-    t = SC.col2im_inputs(case)
-    return _cached(("col2im", name), lambda: sums_of(lambda cast: {"dx": R.col2im_taps(cast(t), H, W, R_, S, ph, pw, dh, dw)}, {"dx": R_ * S}))
 
 
 def axpby_bound(ax, by=None):
     return 2 * ULP * (ax.double().abs() + (0 if by is None else by.double().abs()))
-
-
-# ---- buffers with canaries -------------------------------------------------------------------------------------------------------------------
-def carve(dev, *numels):
-    """-> ([flat float32 views of one allocation, 256-byte aligned, GUARD floats of canary around each], intact()): a 16-byte store past the
-    end of a buffer, or before its start, lands in a canary"""
-    offs, pos = [], GUARD
-    for n in numels:
-        offs.append(pos)
-        pos += (n + 63) // 64 * 64 + GUARD
-    buf = torch.full((pos,), CANARY, dtype=torch.float32, device=dev)
-    views = [buf[o:o + n] for o, n in zip(offs, numels)]
-
-    def intact():
-        live = torch.zeros(pos, dtype=torch.bool, device=dev)
-        for o, n in zip(offs, numels):
-            live[o:o + n] = True
-        return bool((buf[~live] == CANARY).all())
-    return views, intact
-
-
-def put(view, t):
-    view.copy_(t.reshape(-1).to(view.device))
-    return view
 
 
 def _numel(shape):

@@ -3,7 +3,6 @@ in fp64, their fp32 fixed-order twins against the fp64 ones, the bookkeeping of 
 tables reach every regime the kernels have, the second trip of the grid-stride loops included), and the sensitivity of those tables:
 eighteen plausible kernel flaws, seeded into copies of the restatements that live in this file only, each move some case past the bound
 tests/test_resample_glue_fp64_gpu.py holds that case to by SENSITIVITY_FACTOR or more, or flip one of its exact comparisons."""
-import importlib.util
 import math
 import os
 
@@ -14,21 +13,15 @@ import torch.nn.functional as F
 
 from oracle import resample_cases as SC
 from oracle import resample_ref as R
+import _resample_glue_checks as G  # the references and bounds the GPU file holds the device to
+from _fp64 import _d, _f, _ratio, cpu_threads
+from _guarded import CANARY
 
 SENSITIVITY_FACTOR = 10.0
 TOL = 1e-10
 
 
-def _gpu_module():
-    """the GPU test's references and bounds (importing it needs no GPU)"""
-    spec = importlib.util.spec_from_file_location("resample_glue_fp64_gpu_refs", os.path.join(os.path.dirname(os.path.abspath(__file__)), "test_resample_glue_fp64_gpu.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-G = _gpu_module()
-G._cpu_threads()
+cpu_threads()
 
 
 def _leaf(t):
@@ -127,7 +120,7 @@ def test_nhwc_restatement_matches_torch(case):
         m = None if mask is None else mask.double().abs()
         by = R.sum_bound(kk + 3, R.act_avgpool_fwd(x.double().abs(), m, SC.NONE, 0.0, *prm["k"]))
         bx = R.sum_bound(4, R.act_avgpool_bwd(dy.double().abs(), x.double().abs() + 1, m, SC.NONE, 0.0, *prm["k"]))
-        assert G._ratio(exact["y"], got["y"], by) <= 1.0 and G._ratio(exact["dx"], got["dx"], bx) <= 1.0, "%s: fp32 twin off the fp64 value" % name
+        assert _ratio(exact["y"], got["y"], by) <= 1.0 and _ratio(exact["dx"], got["dx"], bx) <= 1.0, "%s: fp32 twin off the fp64 value" % name
     for k, v in exact.items():
         if op != "act_avgpool":
             assert G.same(v, got[k].to(v.dtype)), "%s %s: the exact reference is not the fp64 restatement rounded" % (name, k)
@@ -150,7 +143,7 @@ def test_channel_and_layout_restatements_match_torch():
         _close(R.pad_channels(src, Cpad), F.pad(src, (0, Cpad - C)), "pad_channels")
     for case in SC.REDUCE_CASES:
         name, N, HW, Cs, soff, Cn, acc = case
-        out, src, prev = G.reduce_values(case, G._d)
+        out, src, prev = G.reduce_values(case, _d)
         want = src.double().view(N, HW, Cs)[:, :, soff:soff + Cn].sum(1) + (prev.double() if acc else 0)
         _close(out["out"], want, "reduce " + name)
     for case in SC.ONEHOT_CASES:
@@ -188,7 +181,7 @@ def test_fused_weight_and_col2im_restatements_match_torch():
         _close(R.fused_weight_bwd(dw4.double(), SC.FUSED_MULT, prev.double()), wl.grad + prev.double(), "fused bwd acc")
         mult = float(np.float32(SC.FUSED_MULT))
         absd = R.fused_weight_bwd(dw4.double().abs(), mult, prev.double().abs())
-        assert G._ratio(R.fused_weight_bwd_f32(dw4, mult, prev), R.fused_weight_bwd(dw4.double(), mult, prev.double()), R.sum_bound(7, absd)) <= 1.0
+        assert _ratio(R.fused_weight_bwd_f32(dw4, mult, prev), R.fused_weight_bwd(dw4.double(), mult, prev.double()), R.sum_bound(7, absd)) <= 1.0
     for case in SC.COL2IM_CASES:
         name, N, H, W, R_, S, ph, pw, dh, dw = case
         t = SC.col2im_inputs(case).double()
@@ -231,7 +224,7 @@ def test_glue_restatements():
         bank, ij, w = SC.style_mix_inputs(case)
         want = bank.double()[ij[0].long()] * w[0].double()[:, None] + bank.double()[ij[1].long()] * w[1].double()[:, None]
         _close(R.style_mix(bank.double(), ij, w.double()), want)
-        assert G._ratio(R.style_mix_f32(bank, ij, w), want, R.sum_bound(2, R.style_mix(bank.double().abs(), ij, w.double().abs()))) <= 1.0
+        assert _ratio(R.style_mix_f32(bank, ij, w), want, R.sum_bound(2, R.style_mix(bank.double().abs(), ij, w.double().abs()))) <= 1.0
         assert int(ij[0, 0]) == int(ij[1, 0])
 
 
@@ -407,19 +400,19 @@ def _stale(ref, V):
     """what a kernel whose loop never takes its second trip leaves behind: everything past the first GRID_CAP work items keeps the buffer's
     earlier content (the canary value of the GPU file's buffers)"""
     out = ref.clone().reshape(-1)
-    out[SC.GRID_CAP * V:] = G.CANARY
+    out[SC.GRID_CAP * V:] = CANARY
     return out.reshape(ref.shape)
 
 
 def _moved(flawed, ent):
     """|flawed - reference| / bound, worst element: what the GPU test would report for a kernel with this flaw"""
     ref, yard, bound = ent
-    return G._ratio(flawed, ref, bound)
+    return _ratio(flawed, ref, bound)
 
 
 def _flaw_results():
     """flaw -> (how far it moves its case: worst |err| / bound, or inf for an exact comparison that flips; the same measure without the flaw)"""
-    d, INF = G._d, float("inf")
+    d, INF = _d, float("inf")
     flip = lambda bad, good, want: (INF if not G.same(bad, want) else 0.0, INF if not G.same(good, want) else 0.0)
     res = {}
     c = _case("avgpool_k22_c8")
@@ -462,7 +455,7 @@ def _flaw_results():
     c = [k for k in SC.COPY_CASES if k[0] == "soff_doff"][0]
     src, dst = SC.copy_inputs(c)
     a = (src, c[3], dst, c[5], c[6], c[7], c[8], c[9])
-    res["copy_ignores_doff"] = flip(copy_channels(*a, flaw="copy_ignores_doff"), copy_channels(*a), G.copy_values(c, G._f)["dst"])
+    res["copy_ignores_doff"] = flip(copy_channels(*a, flaw="copy_ignores_doff"), copy_channels(*a), G.copy_values(c, _f)["dst"])
     c = SC.ONEHOT_CASES[0]
     lab, _ = SC.onehot_labels(c)
     res["onehot_swaps_L_and_B"] = flip(onehot(lab, c[3], "onehot_swaps_L_and_B"), onehot(lab, c[3]), R.onehot(lab, c[3]))

@@ -2,9 +2,9 @@
 hwg_dtw_align, hwg_gt_counts, hwg_loss_fwd / _bwd, hwg_masked_l1_fwd / _bwd, hwg_spectral_update / _update_to / _update_multi, hwg_scale_by_ptr,
 hwg_spectral_bwd / _bwd_multi, hwg_pixelnorm_fwd / _bwd - called at the C ABI through L.query on guarded buffers, against the fp64 restatements
 of oracle/seq_ref.py. The protocol (guarded operands, a workspace of exactly the queried size poisoned with NaN, a second call on a zero-filled
-workspace, the under-run by one byte and the null workspace) is that of tests/test_norm_abi_fp64_gpu.py, loaded from there with its buffers;
+workspace, the under-run by one byte and the null workspace) is that of tests/_guarded.py, with its buffers;
 case tables: oracle/abi_cases.py, checked on the CPU by tests/test_abi_cases_cpu.py; the bounds are BOUNDS / DERIVED of
-tests/test_seq_loss_fp64_gpu.py, imported: the same kernels and the same arithmetic. The library's default tuning only.
+tests/_seq_loss_checks.py, which tests/test_seq_loss_fp64_gpu.py holds the same kernels to: the same arithmetic. The library's default tuning only.
 
 Per entry, what is asserted beyond the protocol, and the worst ratio measured on an MI355X (relative L2 and max|err| / max|ref|, each divided
 by its bound, unless a per-element bound is stated; every case prints its own line, kept in profiles/norm_seq_abi_fp64.txt):
@@ -39,28 +39,21 @@ by its bound, unless a per-element bound is stated; every case prints its own li
   hwg_pixelnorm_fwd, _bwd       BOUNDS["pixelnorm_fwd" / "pixelnorm_grad" / "pixelnorm_grad_c1"], bits of ops.pixel_norm                     [y 0.26 / 0.25, dx 0.26 / 0.25]
   refusals                      hwg_loss_bwd with a mode outside 0..4 or a pair mode without b, ctc_bwd with a non-positive size:
                                 HWG_ERR_ARG before any launch, outputs still NaN."""
-import os
-import sys
-
 import numpy as np
 import pytest
 import torch
 
+import _fg_mask_ref as FG
 from oracle import abi_cases as AC
 from oracle import seq_cases as SC
 from oracle import seq_ref as R
+from _fp64 import SECOND, U, _f32, _ratio, cpu_threads, report
 from _gpu_tidy import leave_nothing_behind  # noqa: F401  (module-scoped, autouse)
-
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import _fg_mask_ref as FG  # noqa: E402
-import test_norm_abi_fp64_gpu as P  # noqa: E402  (the protocol and its buffers; importing it needs no GPU)
+from _guarded import NAN, Guarded, bits_differ, protocol, refused, same_bits
+from _seq_loss_checks import ACC_CASES, BOUNDS, DERIVED, _leaf
 
 pytestmark = pytest.mark.gpu
 
-SL = P._load("test_seq_loss_fp64_gpu.py")
-BOUNDS, DERIVED, _f32, _leaf = SL.BOUNDS, SL.DERIVED, SL._f32, SL._leaf
-Guarded, protocol, refused, report, bits_differ, same_bits = P.Guarded, P.protocol, P.refused, P.report, P.bits_differ, P.same_bits
-U, SECOND = P.U, P.SECOND
 F32, I32, I64 = torch.float32, torch.int32, torch.int64
 GOUT = SC.LOSS_GOUT
 
@@ -76,7 +69,7 @@ def _lib():
 
 def _worst(got, want, bound):
     """worst |err| / bound over the elements, per-element bounds"""
-    return P.F._ratio(got.reshape(want.shape), want, bound)
+    return _ratio(got.reshape(want.shape), want, bound)
 
 
 # ---- log-softmax -----------------------------------------------------------------------------------------------------------------------------------
@@ -100,7 +93,7 @@ def test_log_softmax_entries_both_row_orders(cuda, case):
         dx = protocol(G2, "%s hwg_log_softmax_bwd transpose %d" % (name, tr),
                       lambda ws, n: L.query("hwg_log_softmax_bwd", h["dy"], h["y"], h["dx"], rows, C, B, T, tr, G2.st))["dx"]
         out[tr] = (y, dx)
-    P.NA._cpu_threads()
+    cpu_threads()
     x64 = _leaf(x)
     yr = R.log_softmax_tbc(x64)
     yr.backward(gy.double())
@@ -141,7 +134,7 @@ def _ctc_pair(G, name, fwd, bwd, e_fwd, e_bwd):
     """forward under the full protocol, once more on a poisoned workspace, then backward on the workspace that call left -> (loss, grad)"""
     loss = protocol(G, "%s %s" % (name, e_fwd), fwd(e_fwd), mine=("loss",))["loss"]
     G.reset()
-    G.ws_fill(P.NAN)
+    G.ws_fill(NAN)
     assert fwd(e_fwd)(G.ws, G.need) == 0
     torch.cuda.synchronize()
     assert same_bits(G.get("loss"), loss)
@@ -160,7 +153,7 @@ def test_ctc_entries_on_a_poisoned_workspace(cuda, case):
     assert not differ, "%s: hwg_ctc_fwd_beta + hwg_ctc_bwd_grad differ from hwg_ctc_fwd + hwg_ctc_bwd in %s" % (name, differ)
     for b in range(B):          # behind an item's input length: +0, bit for bit
         assert not grad[in_len[b]:, b].view(I32).any(), "%s: the gradient behind in_len of item %d is not +0" % (name, b)
-    P.NA._cpu_threads()
+    cpu_threads()
     lp64 = _leaf(lp)
     lr, nll = R.ctc(lp64, tg, in_len, tg_len)
     (lr * GOUT).backward()
@@ -265,9 +258,6 @@ def test_loss_entries_on_guarded_buffers_vs_fp64(cuda, case):
     assert not bad, "%s vs fp64: %s" % (name, "; ".join(bad))
 
 
-ACC_CASES = [c for c in AC.LOSS_CASES if c[2] in (255, 4097)]
-
-
 @pytest.mark.parametrize("case", ACC_CASES, ids=[c[0] for c in ACC_CASES])
 def test_loss_entries_accumulate_into_prefilled_outputs(cuda, case):
     """accumulate = 1: out0 + v and da0 + d, db0 - d, one rounded sum more than the plain call (the bound of the module docstring)"""
@@ -364,7 +354,7 @@ def _update(dev, w, u, v, R_, K, variant):
 
 
 def _sn_reference(w, u, v, gw):
-    P.NA._cpu_threads()
+    cpu_threads()
     w64 = _leaf(w)
     ref = R.spectral(w64, u.double(), v.double(), _f32(SC.SN_EPS))
     ref[3].backward(gw.double())
@@ -456,7 +446,7 @@ def test_spectral_multi_entries_on_guarded_buffers(cuda):
         sigmas.append(out["sig"][2 * i:2 * i + 1].clone())
     pad = out["copies"].clone()
     for i, (R_, K) in enumerate(shapes):
-        pad[spans[i]:spans[i] + R_ + K] = P.NAN
+        pad[spans[i]:spans[i] + R_ + K] = NAN
     assert bool(torch.isnan(pad).all()), "hwg_spectral_update_multi wrote between the layers' snapshots"
     assert not bad, "hwg_spectral_update_multi vs fp64: %s" % "; ".join(bad)
     # backward: all layers in two launches, bit-identical to the single calls
@@ -479,7 +469,7 @@ def test_spectral_multi_entries_on_guarded_buffers(cuda):
         one_need = int(L.query("hwg_spectral_workspace", R_, K))
         G1 = Guarded(cuda, {q: ins["%s%d" % (q, i)] for q in "gWuvs"}, dict(d=outs["d%d" % i]), one_need)
         o = G1.f
-        G1.ws_fill(P.NAN)
+        G1.ws_fill(NAN)
         assert L.query("hwg_spectral_bwd", o["g"], o["W"], o["u"], o["v"], o["s"], o["d"], R_, K, i % 2, G1.ws, one_need, G1.st) == 0
         torch.cuda.synchronize()
         assert same_bits(G1.get("d"), multi["d%d" % i]) and G1.intact(), "layer %d: hwg_spectral_bwd_multi differs from the single call" % i

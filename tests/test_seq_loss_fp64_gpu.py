@@ -1,71 +1,24 @@
 """GPU: the sequence, loss and spectral-norm kernels (csrc/seq_ops.hip, csrc/spectral_loss.hip) against the fp64 CPU restatements of
 oracle/seq_ref.py, at the training step's shapes and at every loop-trip, length and shape regime of the kernels (case tables and the regimes
 they cover: oracle/seq_cases.py; the restatements, the tables and their sensitivity to seeded flaws are checked on the CPU by
-tests/test_seq_loss_ref_cpu.py). The library's default path only.
+tests/test_seq_loss_ref_cpu.py). The bounds (BOUNDS / DERIVED, shared with tests/test_seq_loss_abi_fp64_gpu.py) are those of
+tests/_seq_loss_checks.py. The library's default path only.
 
 Every floating-point output is compared by its relative L2 error and by max|err| / max|ref|; one line per case is printed. Integer outputs
 (argmax, the DTW alignment and its run-length counts) and the zeros the kernels promise (the CTC gradient behind an input length, loss and
 gradient of an infeasible CTC batch, the gradient at an exact tie of L1 / hinge, pixel norm of a zero row) are compared with torch.equal.
 The CTC lines also carry the error of torch's own fp32 CPU ctc_loss on the same inputs: the yardstick for what fp32 log-space arithmetic
 costs at that shape, never the bound."""
-import os
-
 import pytest
 import torch
 import torch.nn.functional as F
 
 from oracle import seq_cases as SC
 from oracle import seq_ref as R
+from _fp64 import YARDSTICK_FACTOR, _f32, cpu_threads
+from _seq_loss_checks import BOUNDS, DERIVED, ULP, _leaf
 
 pytestmark = pytest.mark.gpu
-
-ULP = 2.0 ** -23
-# (relative L2, max|err| / max|ref|), derived: the expected value is an fp64-exact quantity rounded to fp32 once, or twice where noted
-DERIVED = {
-    # sum of fp32 terms in double, then one rounding of the mean: |a - b|, 1 - a, 1 + a are each one fp32 rounding of an exact difference
-    # (non-negative terms: the sum keeps the relative error of its terms), the mean of a itself has exact terms
-    "loss_value": (ULP, ULP),
-    # (a - b)^2: the difference and its square are rounded, then the mean: one more ulp
-    "loss_value_mse": (2 * ULP, 2 * ULP),
-    # +-float(gout * scale / n): scale / n is rounded once, gout = 0.5 is a power of two
-    "loss_grad_const": (ULP, ULP),
-}
-# (relative L2, max|err| / max|ref|) per family: 4x the worst case measured on an MI355X (in brackets), rounded down to two digits.
-# The flaws tests/test_seq_loss_ref_cpu.py seeds move some case of the family concerned by 10x its bound or more.
-BOUNDS = {
-    "lsm_fwd": (2.1e-7, 4.3e-7),          # [5.3e-8, 1.1e-7]
-    "lsm_grad": (7.9e-6, 2.3e-5),         # [2.0e-6, 5.8e-6]  (the 30 x randn + 60 logits: log-probs near -200 carry an absolute error of 1e-5 into exp)
-    "ctc_plain_loss": (7.3e-7, 7.3e-7),   # [1.8e-7, 1.8e-7]  unit-variance logits
-    "ctc_plain_grad": (2.5e-4, 6.4e-4),   # [6.3e-5, 1.6e-4]  d log-probs and d logits; torch's fp32 ctc_loss: 4.2e-5 on the same case
-    "ctc_peaked_loss": (4.6e-7, 4.6e-7),  # [1.2e-7, 1.2e-7]  peaked logits, 3 x randn over 281 states
-    "ctc_peaked_grad": (1.6e-3, 3.1e-3),  # [4.0e-4, 7.9e-4]  torch's fp32 ctc_loss: 4.0e-4
-    "ctc_long_loss": (1.6e-6, 1.6e-6),    # [4.0e-7, 4.0e-7]  600 steps of 4 x randn
-    "ctc_long_grad": (1.1e-2, 2.2e-2),    # [2.8e-3, 5.6e-3]  torch's fp32 ctc_loss: 2.8e-3
-    "mse_grad": (2.8e-7, 6.7e-7),         # [7.0e-8, 1.7e-7]
-    "sn_uv": (1.2e-6, 1.9e-6),            # [3.0e-7, 4.8e-7]  persisted u, v after one and after two iterations
-    "sn_sigma": (4.2e-7, 4.2e-7),         # [1.1e-7, 1.1e-7]  sigma and 1 / sigma
-    "sn_w": (4.3e-7, 5.1e-7),             # [1.1e-7, 1.3e-7]
-    "sn_grad": (5.0e-7, 6.4e-7),          # [1.3e-7, 1.6e-7]  returned and added to a pre-filled parameter gradient
-    "pixelnorm_fwd": (2.2e-7, 4.6e-7),    # [5.6e-8, 1.2e-7]
-    "pixelnorm_grad": (2.2e-7, 3.8e-7),   # [5.7e-8, 9.7e-8]
-    # one channel: y = x / sqrt(x^2 + eps) is +-1 and dx = dy eps / (x^2 + eps)^1.5 is 1e-8 of the two terms dy / d and x^2 dy / d^3 it is the
-    # difference of - no fp32 evaluation keeps a digit of it. The error is measured against those terms (max |dy / d|), not against dx.
-    "pixelnorm_grad_c1": (2.3e-7, 2.5e-7),  # [5.8e-8, 6.4e-8]
-}
-YARDSTICK_FACTOR = 10.0      # a CTC gradient this many times worse than torch's fp32 ctc_loss is a finding, not something a bound absorbs
-
-
-def _f32(v):
-    """a Python float as the kernels receive it"""
-    return float(torch.tensor(v, dtype=torch.float32))
-
-
-def _cpu_threads():
-    torch.set_num_threads(min(16, os.cpu_count() or 1))
-
-
-def _leaf(t):
-    return t.double().clone().requires_grad_(True)
 
 
 def _errs(got, want):
@@ -105,7 +58,7 @@ def test_log_softmax_vs_fp64(cuda, case):
     xg = x.to(cuda).requires_grad_(True)
     y = ops.log_softmax_tbc(xg)
     y.backward(gy.to(cuda))
-    _cpu_threads()
+    cpu_threads()
     x64 = _leaf(x)
     yr = R.log_softmax_tbc(x64)
     yr.backward(gy.double())
@@ -117,7 +70,7 @@ def _ctc_reference(case):
     """fp64: loss, d (0.5 loss) / d log-probs as the kernels report it, d (0.5 loss) / d logits; and what torch's fp32 CPU ctc_loss makes of
     the same logits (None for the infeasible case, where torch's gradient is NaN)"""
     name, T, B, C, Lmax, tg_len, in_len, kind, targets, family = case
-    _cpu_threads()
+    cpu_threads()
     x, tg = SC.ctc_inputs(case)
     x64 = _leaf(x)
     lp = R.log_softmax_tbc(x64)
@@ -202,7 +155,7 @@ def _sn_checks(label, got, ref, grad_got, grad_want):
 def _sn_reference(inputs, eps):
     """two successive fp64 iterations (the second on the moved weight, from the first's u', v') -> [(R.spectral's tuple, d / d w_bar)]"""
     w1, w2, u, v, g1, g2 = inputs
-    _cpu_threads()
+    cpu_threads()
     out, u64, v64 = [], u.double(), v.double()
     for w, gw in ((w1, g1), (w2, g2)):
         w64 = _leaf(w)

@@ -12,14 +12,11 @@ import torch.nn.functional as F
 
 from oracle import seq_cases as SC
 from oracle import seq_ref as R
+from _seq_loss_checks import BOUNDS, _leaf
 
 F32_ULP = 2.0 ** -23
 # a seeded flaw must move some case by this multiple of the bound tests/test_seq_loss_fp64_gpu.py holds that case to
 SENSITIVITY_FACTOR = 10.0
-
-
-def _leaf(t):
-    return t.double().clone().requires_grad_(True)
 
 
 def _close(a, b, tol):
@@ -266,15 +263,6 @@ def _spectral_flawed(w_bar, u, v, eps, sigma_from_old_u=False):
     return u1, v1, sigma, wsn
 
 
-def _gpu_bounds():
-    """the bounds the GPU test holds each family to, read from its module (importing it needs no GPU)"""
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("seq_loss_fp64_gpu_bounds", os.path.join(os.path.dirname(os.path.abspath(__file__)), "test_seq_loss_fp64_gpu.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod.BOUNDS
-
-
 def _ctc_moves(case, **flaw):
     """relative L2 moves of (loss, d loss / d logits) of one CTC case under a flaw"""
     ref = _ctc_reference(case)
@@ -294,7 +282,7 @@ FEASIBLE = [c for c in SC.CTC_CASES if c[9] is not None]
 
 @pytest.mark.parametrize("flaw", ["skip_over_repeats", "nll_at_last_row", "no_clamp"])
 def test_ctc_cases_notice_a_seeded_flaw(flaw):
-    bounds = _gpu_bounds()
+    bounds = BOUNDS
     hit = []
     for case in FEASIBLE:
         if case[1] > 300:
@@ -323,7 +311,7 @@ def test_loss_cases_notice_a_dropped_partial_block():
 
 
 def test_spectral_cases_notice_sigma_from_the_old_u():
-    bounds = _gpu_bounds()
+    bounds = BOUNDS
     hit = []
     for R_, K in SC.SN_SHAPES:
         w1, w2, u, v, g1, g2 = (t.double() for t in SC.sn_inputs("single", R_, K))

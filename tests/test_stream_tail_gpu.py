@@ -6,7 +6,7 @@ Max-pool backward is a routing of dy: compared with torch.equal on the int32 vie
 torch.nn.functional.max_pool2d on the CPU. With relu=True the kernels' definition is dx = scatter(dy * [y > 0]), y the pooled output after
 the ReLU: the reference gates dy the same way (one exact fp32 product) before torch's backward; a window whose maximum is NaN has y = 0.
 The multi-tensor kernels write every element from that element alone: the same call through two chunk tables must give the same bits.
-Adam is held to the per-element bounds of tests/test_optim_rng_fp64_gpu.py (adam_bounds, restated here). The two CTC paths must agree bit
+Adam is held to the per-element bounds of tests/test_optim_rng_fp64_gpu.py (adam_bounds of tests/_optim_rng_checks.py, restated here). The two CTC paths must agree bit
 for bit and sit within the tolerance tests/test_ops_gpu.py::test_log_softmax_ctc holds ops.ctc_loss to against F.ctc_loss."""
 import numpy as np
 import pytest
@@ -14,6 +14,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import optim_ref as R
+from _fp64 import _f32
 
 pytestmark = pytest.mark.gpu
 
@@ -149,7 +150,7 @@ def _mt_host_buffers(lay):
 
 
 def _adam_bounds(p0, g, m0, v0, ss, bc2, b1, b2, eps, ref):
-    """tests/test_optim_rng_fp64_gpu.py::adam_bounds, restated: every operation one fp32 rounding, division and square root two"""
+    """tests/_optim_rng_checks.py::adam_bounds, restated: every operation one fp32 rounding, division and square root two"""
     pr, _, mr, vr = ref
     c1 = 1.0 - b1
     bm = SLACK * E * (2 * ((g - m0) * c1).abs() + mr.abs())
@@ -158,10 +159,6 @@ def _adam_bounds(p0, g, m0, v0, ss, bc2, b1, b2, eps, ref):
     u = ss * mr / denom
     bp = SLACK * (E * pr.abs() + 9.75 * E * u.abs() + ss * bm / denom)
     return bm, bv, bp
-
-
-def _f32(v):
-    return float(torch.tensor(v, dtype=torch.float32))
 
 
 def test_mt_kernels_same_bits_through_two_chunk_tables(cuda):

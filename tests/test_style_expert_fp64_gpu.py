@@ -3,7 +3,7 @@ AdaIN LinearBank, the MLPChain) and the expert-bank kernels (csrc/expert_bank.hi
 gradient and its reduce, gather_rows_ptr, segment_accumulate_ptr, and run_experts end to end) against the fp64 CPU restatements of
 oracle/style_ref.py, at the step's shapes and at every dispatch regime of the kernels (case tables and the regimes they cover:
 oracle/style_cases.py; the restatements, the tables and their sensitivity to seeded flaws are checked on the CPU by
-tests/test_style_expert_ref_cpu.py). The library's default path only.
+tests/test_style_expert_ref_cpu.py; the references and their bounds: tests/_style_expert_checks.py). The library's default path only.
 
 One line per case is printed: per output the relative L2 error and max|err| / max|ref| against fp64, the yardstick (the same restatement in
 fp32 torch on the CPU against the same fp64 value) and the worst |err| / bound over the elements. No bound comes from the kernels:
@@ -23,62 +23,19 @@ fp32 torch on the CPU against the same fp64 value) and the worst |err| / bound o
 (No errors measured on an MI355X stand beside the families yet: every case prints its own on the line it writes.)
 Every output that is a sum is also held to YARDSTICK_FACTOR times its yardstick in relative L2 (a yardstick of exactly zero: the derived
 bound alone)."""
-import os
-
 import numpy as np
 import pytest
 import torch
 
 from oracle import style_cases as SC
 from oracle import style_ref as R
+from _fp64 import YARDSTICK_FACTOR, _a, _d, _f, _ratio_rows, cpu_threads
+from _style_expert_checks import (accumulate_reference, bank_reference, chain_reference, conv_reference, entry, seg_reference,
+                                  window_reference)
 
 pytestmark = pytest.mark.gpu
 
 ULP = 2.0 ** -23
-YARDSTICK_FACTOR = 10.0      # the project's constant (tests/test_seq_loss_fp64_gpu.py): absorbs summation-order differences between a kernel's
-                             # sequential / matrix-core chains and torch's blocked sums
-
-
-def _cpu_threads():
-    torch.set_num_threads(min(16, os.cpu_count() or 1))
-
-
-def _d(t):
-    return t.double()
-
-
-def _f(t):
-    return t.float()
-
-
-def _a(t):
-    return t.double().abs()
-
-
-def _rel(got, want):
-    d = got.detach().cpu().double() - want.double()
-    if not bool(torch.isfinite(d).all()):
-        return float("inf")
-    return float(d.norm()) / max(float(want.double().norm()), 1e-300)
-
-
-def _ratio(got, want, bound):
-    """worst |err| / bound over the elements (an element with a bound of 0 must be exact); a bound with one dimension less than the output
-    holds the L2 norm of the error of every row"""
-    err = (got.detach().cpu().double() - want).abs()
-    if bound.dim() == err.dim() - 1:
-        err = err.norm(dim=-1)
-    if not bool(torch.isfinite(err).all()):
-        return float("inf")
-    if err.numel() == 0:
-        return 0.0
-    r = torch.where(bound > 0, err / bound.clamp_min(1e-300), torch.where(err > 0, torch.full_like(err, float("inf")), torch.zeros_like(err)))
-    return float(r.max())
-
-
-def entry(ref, yard32=None, bound=None):
-    """one output of a reference: the fp64 value, the yardstick (relative L2 of the fp32 CPU restatement, None: not a sum), the bound"""
-    return (ref, None if yard32 is None else _rel(yard32, ref), bound)
 
 
 def _kind(name):
@@ -105,7 +62,7 @@ def _check(label, outs, refs, note=""):
                 if rel > YARDSTICK_FACTOR * yard:
                     bad.append("%s: rel L2 %.3e is %.1f x the fp32 yardstick %.3e" % (name, rel, rel / yard, yard))
         if bound is not None:
-            r = _ratio(got, want, bound)
+            r = _ratio_rows(got, want, bound)
             txt += " e/b %.2g" % r
             score = max(score, r)
             if not r <= 1.0:
@@ -116,126 +73,6 @@ def _check(label, outs, refs, note=""):
     assert not bad, "%s vs fp64: %s" % (label, "; ".join(bad))
 
 
-_REF = {}
-
-
-def _cached(key, fn):
-    if key not in _REF:
-        _cpu_threads()
-        _REF[key] = fn()
-    return _REF[key]
-
-
-# ---- references (also used, without a GPU, by tests/test_style_expert_ref_cpu.py: its seeded flaws are measured against these bounds) --------
-def conv_values(case, cast, fwd=R.grouped_conv_fwd, wgrad=R.grouped_conv_wgrad):
-    name, Cin, Cout, S, R_, plan, bias = case
-    x, dy, Ws, bs, gW, gb = SC.conv_inputs(case)
-    cls = SC.plan_cls(plan, R_)
-    X, DY, W = cast(x), cast(dy), [cast(w) for w in Ws]
-    out = {"y": fwd(X, cls, W, [cast(b) for b in bs] if bias else None, S), "dx": R.grouped_conv_dgrad(DY, cls, W, S)}
-    for e, (dW, db) in wgrad(DY, X, cls, S).items():
-        out["dW%d" % e] = cast(gW[e]) + dW
-        if bias:
-            out["db%d" % e] = cast(gb[e]) + db
-    return out
-
-
-def conv_reference(case):
-    def make():
-        name, Cin, Cout, S, R_, plan, bias = case
-        ref, yard, absv = conv_values(case, _d), conv_values(case, _f), conv_values(case, _a)
-        rows = {e: n * R_ for e, n in SC.PLANS[plan][R_].items()}
-        K = {"y": Cin * S + 1, "dx": Cout * S}
-        return {k: entry(v, yard[k], R.sum_bound(K[k] if k in K else rows[int(k[2:])] + 1, absv[k])) for k, v in ref.items()}
-    return _cached(("conv", case[0]), make)
-
-
-def accumulate_reference(C):
-    def make():
-        g = SC.gen("accumulate_%d" % C)
-        cls = np.concatenate([np.full(n, e, dtype=np.int64) for e, n in sorted(SC.ACCUMULATE_RUNS.items())])
-        rows = torch.randn(cls.size, C, generator=g)
-        pre = torch.randn(SC.E, C, generator=g) * 3
-        vals = [{e: cast(pre[e]) + s for e, s in R.segment_accumulate(cast(rows), cls).items()} for cast in (_d, _f, _a)]
-        refs = {"g%d" % e: entry(vals[0][e], vals[1][e], R.sum_bound(SC.ACCUMULATE_RUNS[e] + 1, vals[2][e])) for e in vals[0]}
-        return cls, rows, pre, refs
-    return _cached(("acc", C), make)
-
-
-def window_reference(case, scatter=R.scatter_windows):
-    def make():
-        name, B, Wx, C, w = case
-        x, ib, ip, dp, n_in = SC.window_inputs(case)
-        vals = [scatter(cast(dp), ib, ip, w, B, Wx) for cast in (_d, _f, _a)]
-        return R.gather_windows(x, ib, ip, w), {"dx": entry(vals[0], vals[1], R.sum_bound(2 * w + 1, vals[2]))}
-    return _cached(("win", case[0], scatter), make)
-
-
-def seg_reference(case, fwd=R.segment_mean):
-    def make():
-        name, n, B, C, kind = case
-        v, wgt, seg, dout = SC.seg_inputs(case)
-        out64, ws64 = fwd(_d(v), _d(wgt), seg, B)
-        out32, ws32 = fwd(v, wgt, seg, B)
-        out_b, ws_rel = R.segment_mean_bound(_d(v), _d(wgt), seg, B)
-        dv64 = R.segment_mean_bwd(_d(dout), _d(wgt), seg, ws64)
-        dv32 = R.segment_mean_bwd(dout, wgt, seg, ws32)
-        # dv = wgt / wsum * dout: the kernel's wsum carries its relative error, the division and the product one rounding each
-        dv_b = dv64.abs() * (2 * ws_rel[seg.long()] + 3 * R.U)[:, None]
-        return {"out": entry(out64, out32, out_b), "dv": entry(dv64, dv32, dv_b)}
-    return _cached(("seg", case[0], fwd), make)
-
-
-def bank_values(case, cast, fwd=R.linear_bank_fwd, bwd=R.linear_bank_bwd):
-    name, B, I, O, halves, unused, frozen, xgrad, backward = case
-    x, Ws, bs, dys, gW, gb = SC.bank_inputs(case)
-    X, W = cast(x), [cast(w) for w in Ws]
-    out = {"y%d_%d" % (l, h): t for l, parts in enumerate(fwd(X, W, [cast(b) for b in bs], halves)) for h, t in enumerate(parts)}
-    if backward:
-        dx, dWs, dbs = bwd(X, W, [[cast(p) if p is not None else None for p in parts] for parts in dys], halves)
-        if xgrad:
-            out["dx"] = dx
-        for l in range(len(O)):
-            if l not in frozen:
-                out["dW%d" % l] = cast(gW[l]) + dWs[l]
-            if frozen.get(l) != "all":
-                out["db%d" % l] = cast(gb[l]) + dbs[l]
-    return out
-
-
-def bank_reference(case):
-    def make():
-        name, B, I, O, halves, unused, frozen, xgrad, backward = case
-        ref, yard, absv = bank_values(case, _d), bank_values(case, _f), bank_values(case, _a)
-        K = lambda k: I + 1 if k[0] == "y" else sum(O) if k == "dx" else B + 1
-        return {k: entry(v, yard[k], R.sum_bound(K(k), absv[k])) for k, v in ref.items()}
-    return _cached(("bank", case[0]), make)
-
-
-def chain_values(case, cast, passes=2, fwd=R.mlp_chain_fwd, bwd=R.mlp_chain_bwd):
-    """forward output, and after `passes` backward passes in a row: d x and the parameter gradients added to their pre-filled values"""
-    name, D, B, L, frozen, backward = case
-    x, Ws, bs, dout, gW, gb = SC.chain_inputs(case)
-    W, Bv = [cast(w) for w in Ws], [cast(b) for b in bs]
-    acts = fwd(cast(x), W, Bv, SC.CHAIN_SLOPE)
-    out = {"h": acts[-1]}
-    if backward:
-        dx, dWs, dbs = bwd(cast(dout), acts, W, SC.CHAIN_SLOPE)
-        out["dx"] = passes * dx
-        for l in range(L):
-            if l != frozen:
-                out["dW%d" % l] = cast(gW[l]) + passes * dWs[l]
-                out["db%d" % l] = cast(gb[l]) + passes * dbs[l]
-    return out, acts
-
-
-def chain_reference(case):
-    def make():
-        x, Ws, bs, dout, gW, gb = SC.chain_inputs(case)
-        (ref, acts), (yard, _) = chain_values(case, _d), chain_values(case, _f)
-        hb = R.chain_fwd_bound(acts, [_d(w) for w in Ws], [_d(b) for b in bs])
-        return {k: entry(v, yard[k], hb if k == "h" else None) for k, v in ref.items()}
-    return _cached(("chain", case[0]), make)
 
 
 # ---- grouped Conv1d --------------------------------------------------------------------------------------------------------------------
@@ -337,7 +174,7 @@ def test_grouped_conv_autograd_step_layers_vs_fp64(cuda, expert_modules, layer):
     y = expert_bank._GroupedConv1d.apply(xd, bank, wk, bk, plan, S, S // 2)
     y.backward(dy.view(cls.size, 1, R_, Cout).to(cuda))
     torch.cuda.synchronize()
-    _cpu_threads()
+    cpu_threads()
     present = SC.PLANS["mixed"][R_]
     vals = []
     for cast in (_d, _f, _a):
@@ -397,7 +234,7 @@ def test_run_experts_vs_fp64_per_class_loop(cuda, expert_modules):
     out = expert_bank.run_experts(bank, xd, plan, g1, g2)
     out.backward(dout.to(cuda))
     torch.cuda.synchronize()
-    _cpu_threads()
+    cpu_threads()
     vals = []
     for dt in (torch.float64, torch.float32):
         xs = x.to(dt).requires_grad_(True)

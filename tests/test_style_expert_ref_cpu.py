@@ -2,7 +2,6 @@
 the bookkeeping of the GPU case tables (oracle/style_cases.py: the tables together reach every dispatch regime the kernels have), and the
 sensitivity of those tables: thirteen plausible kernel flaws, seeded by flag into copies of the restatements that live in this file only,
 each move some case past the bound tests/test_style_expert_fp64_gpu.py holds that case to by SENSITIVITY_FACTOR or more."""
-import importlib.util
 import os
 
 import numpy as np
@@ -12,19 +11,10 @@ import torch.nn.functional as F
 
 from oracle import style_cases as SC
 from oracle import style_ref as R
+import _style_expert_checks as G  # the references and bounds the GPU file holds the device to
+from _fp64 import YARDSTICK_FACTOR, _d, _ratio_rows, _rel
 
 SENSITIVITY_FACTOR = 10.0
-
-
-def _gpu_module():
-    """the GPU test's references and bounds (importing it needs no GPU)"""
-    spec = importlib.util.spec_from_file_location("style_expert_fp64_gpu_refs", os.path.join(os.path.dirname(os.path.abspath(__file__)), "test_style_expert_fp64_gpu.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-G = _gpu_module()
 
 
 def _leaf(t):
@@ -379,21 +369,21 @@ def _moves(got, refs):
     worst = 0.0
     for k, (want, yard, bound) in refs.items():
         if bound is not None:
-            worst = max(worst, G._ratio(got[k], want, bound))
+            worst = max(worst, _ratio_rows(got[k], want, bound))
         else:
-            worst = max(worst, G._rel(got[k], want) / (G.YARDSTICK_FACTOR * yard))
+            worst = max(worst, _rel(got[k], want) / (YARDSTICK_FACTOR * yard))
     return worst
 
 
 def test_flawed_copies_without_flaws_are_the_restatements():
     for case in SC.CONV_CASES[:2] + SC.CONV_CASES[10:12]:
-        a, b = G.conv_values(case, G._d), G.conv_values(case, G._d, fwd=grouped_conv_fwd, wgrad=grouped_conv_wgrad)
+        a, b = G.conv_values(case, _d), G.conv_values(case, _d, fwd=grouped_conv_fwd, wgrad=grouped_conv_wgrad)
         assert all(torch.equal(a[k], b[k]) for k in a)
     for case in SC.BANK_CASES[:3]:
-        a, b = G.bank_values(case, G._d), G.bank_values(case, G._d, fwd=linear_bank_fwd, bwd=linear_bank_bwd)
+        a, b = G.bank_values(case, _d), G.bank_values(case, _d, fwd=linear_bank_fwd, bwd=linear_bank_bwd)
         assert all(torch.equal(a[k], b[k]) for k in a)
     for case in SC.CHAIN_CASES[:4]:
-        a, b = G.chain_values(case, G._d)[0], G.chain_values(case, G._d, fwd=mlp_chain_fwd, bwd=mlp_chain_bwd)[0]
+        a, b = G.chain_values(case, _d)[0], G.chain_values(case, _d, fwd=mlp_chain_fwd, bwd=mlp_chain_bwd)[0]
         assert all(torch.equal(a[k], b[k]) for k in a)
     for case in SC.SEG_CASES[:3]:
         v, wgt, seg, dout = SC.seg_inputs(case)
@@ -414,7 +404,7 @@ def test_conv_cases_notice_a_seeded_flaw(flaw):
         if case[0].startswith("step_") and case[0] not in ("step_w1_r5", "step_w3_r5", "step_w5_r1"):
             continue                                    # (the other step layers add nothing here)
         kw = {"fwd": lambda *a: grouped_conv_fwd(*a, flaw=flaw)} if CONV_FLAWS[flaw] == "fwd" else {"wgrad": lambda *a: grouped_conv_wgrad(*a, flaw=flaw)}
-        move = _moves(G.conv_values(case, G._d, **kw), G.conv_reference(case))
+        move = _moves(G.conv_values(case, _d, **kw), G.conv_reference(case))
         if move >= SENSITIVITY_FACTOR:
             hit[case[0]] = move
     print("\n%s moves (case, x bound): %s" % (flaw, ", ".join("%s %.1e" % h for h in hit.items())))
@@ -452,7 +442,7 @@ def test_window_cases_notice_shifted_clipped_windows():
 def test_bank_cases_notice_a_seeded_flaw(flaw):
     hit = {}
     for case in SC.BANK_CASES:
-        got = G.bank_values(case, G._d, fwd=lambda *a: linear_bank_fwd(*a, flaw=flaw), bwd=lambda *a: linear_bank_bwd(*a, flaw=flaw))
+        got = G.bank_values(case, _d, fwd=lambda *a: linear_bank_fwd(*a, flaw=flaw), bwd=lambda *a: linear_bank_bwd(*a, flaw=flaw))
         move = _moves(got, G.bank_reference(case))
         if move >= SENSITIVITY_FACTOR:
             hit[case[0]] = move
@@ -467,7 +457,7 @@ def test_bank_cases_notice_a_seeded_flaw(flaw):
 def test_chain_cases_notice_a_seeded_flaw(flaw):
     hit = {}
     for case in SC.CHAIN_CASES:
-        got = G.chain_values(case, G._d, fwd=lambda *a: mlp_chain_fwd(*a, flaw=flaw), bwd=lambda *a: mlp_chain_bwd(*a, flaw=flaw))[0]
+        got = G.chain_values(case, _d, fwd=lambda *a: mlp_chain_fwd(*a, flaw=flaw), bwd=lambda *a: mlp_chain_bwd(*a, flaw=flaw))[0]
         move = _moves(got, G.chain_reference(case))
         if move >= SENSITIVITY_FACTOR:
             hit[case[0]] = move

@@ -2,8 +2,8 @@
 hwg_store_line_stats, hwg_store_warp_batch, hwg_lines_from_u8, hwg_stretch_onehot - and the clamps of hwg_lines_to_u8, hwg_augment_stats and
 hwg_augment_warp, called at the C ABI through L.query with tables that ops would have refused on the host. Every other test of these files
 goes through ops.* and never reaches this code. The protocol (operands carved out of one allocation with canaries, poisoned outputs, inputs
-bit-identical afterwards, a second call with the same bits, refusals that write nothing) is that of tests/test_norm_abi_fp64_gpu.py, loaded
-from there as tests/test_seq_loss_abi_fp64_gpu.py loads it. Case tables, the slabs and the numpy models: oracle/table_cases.py, checked on
+bit-identical afterwards, a second call with the same bits, refusals that write nothing) is that of tests/_guarded.py, as in
+tests/test_norm_abi_fp64_gpu.py and tests/test_seq_loss_abi_fp64_gpu.py. Case tables, the slabs and the numpy models: oracle/table_cases.py, checked on
 the CPU by tests/test_table_guards_cpu.py - in particular that no bad row names memory outside this file's one allocation even with its
 guard removed: a guard that is wrong shows here as a wrong byte, never as a fault. The offsets that overflow (2^62 and above) are in the CPU
 file only.
@@ -35,11 +35,10 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _fg_mask_ref as FG  # noqa: E402
 import _line_store_ref as LS  # noqa: E402
 import _stretch_ref as ST  # noqa: E402
-import test_norm_abi_fp64_gpu as P  # noqa: E402  (the protocol and its buffers; importing it needs no GPU)
+from _guarded import Guarded, protocol, refused  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-Guarded, protocol, refused = P.Guarded, P.protocol, P.refused
 F32, F64, I32, I64, U8 = torch.float32, torch.float64, torch.int32, torch.int64, torch.uint8
 M = TC.MARGIN
 

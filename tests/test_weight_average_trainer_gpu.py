@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 import torch
 
-from test_reference_checkpoint_cpu import GOLD
+from _reference_checkpoint import GOLD
 
 pytestmark = pytest.mark.gpu
 

@@ -4,7 +4,8 @@ wgrad_narrow_kernel<3,3> / <4,4>, wgrad_c1_rows_kernel, wgrad_c1_kernel, wgrad_d
 and the eight ROWS variants), hwg_conv_wgrad_sets / hwg_wino_wgrad_sets and hwg_colsum - against the fp64 direct form of oracle/conv_ref.py,
 through L.query on the C ABI (never through ops.conv2d), every schedule forced through ops.tuning (case tables, the regimes they cover and the
 restated planners: oracle/wgrad_cases.py; the restatements, the tables and their sensitivity to seeded flaws are checked on the CPU by
-tests/test_wgrad_ref_cpu.py). The buffers, the comparisons and the two conditions are those of tests/test_conv_fp64_gpu.py, loaded from there.
+tests/test_wgrad_ref_cpu.py). The buffers are those of tests/_guarded.py, the comparisons and the two conditions those of
+tests/_conv_checks.py (check()) and tests/_wgrad_checks.py (the references and bounds).
 
 Every call runs on buffers carved out of one allocation with 64-float canaries before, between and after u, v, every dw, every dbias and the
 workspace. The workspace has exactly the bytes the entry's *_workspace query returns and is filled with NaN before every call; dw and dbias are
@@ -39,78 +40,18 @@ partial images summed by the reduce; every reduce schedule adds a range's image 
   hwg_colsum                         -                                                      chunks (fp64 sums, one rounding per chunk, chunks - 1 sums) e/b 0.22, L2 x1.16
                                                                                             + [accumulate]; T = rows
 (measured: worst |err| / bound, worst relative L2 / yardstick over the engine's cases; every case prints its own line.)"""
-import importlib.util
-import os
-
 import numpy as np
 import pytest
 import torch
 
 from oracle import conv_ref as R
 from oracle import wgrad_cases as WC
+from _conv_checks import check
+from _fp64 import _rel
+from _guarded import CANARY, HWG_ERR_ARG, HWG_ERR_WORKSPACE, carve, put, same_bits
+from _wgrad_checks import reference, reference_of
 
 pytestmark = pytest.mark.gpu
-
-
-def _forward_module():
-    """the forward file's buffers, comparisons and conditions (importing it needs no GPU)"""
-    spec = importlib.util.spec_from_file_location("conv_fp64_gpu_shared", os.path.join(os.path.dirname(os.path.abspath(__file__)), "test_conv_fp64_gpu.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-F = _forward_module()
-carve, put, same_bits, _rel, _ratio, check, YARDSTICK_FACTOR, CANARY = F.carve, F.put, F.same_bits, F._rel, F._ratio, F.check, F.YARDSTICK_FACTOR, F.CANARY
-HWG_ERR_ARG, HWG_ERR_WORKSPACE = F.HWG_ERR_ARG, F.HWG_ERR_WORKSPACE
-
-
-# ---- references (also used, without a GPU, by tests/test_wgrad_ref_cpu.py: its seeded flaws are measured against these bounds) ---------------
-def restate(c, u, v, dw0, absolute=False):
-    """the engine's own algorithm in the dtype of the operands: -> dw [R,S,K,C]"""
-    fn = R.wino_wgrad if c["engine"] in ("wino", "s2") else R.wgrad_direct
-    return fn(u, v, WC.geom(c), dw0, absolute=absolute)
-
-
-def terms(c):
-    """T of the bound: [R,S,1,1] pixels whose tap falls inside the image; the Winograd forms contract over the tiles"""
-    N, H, W, C, K, Rr, S = c["shape"]
-    if c["engine"] in ("wino", "s2"):
-        mt = 3 if c["engine"] == "s2" else 2
-        return torch.full((Rr, S, 1, 1), float(N * WC.cdiv(c["P"], mt) * WC.cdiv(c["Q"], mt)), dtype=torch.float64)
-    return R.wgrad_terms(WC.geom(c), N, c["P"], c["Q"], H, W)
-
-
-def reference_of(c, u, v, dw0, db0, T=None):
-    """per set: (fp64 dw, yardstick, bound, fp64 bias gradient, its yardstick, its bound) - the bias entries None without a fused bias gradient"""
-    F._cpu_threads()
-    d = lambda t: None if t is None else t.double()
-    p = WC.plan(c)
-    T = terms(c) if T is None else T
-    out = []
-    for s in range(c["sets"]):
-        us, vs = WC.operands(c, u, v, s)
-        w0 = None if dw0 is None else dw0[s]
-        ref = R.wgrad_direct(d(us), d(vs), WC.geom(c), d(w0))
-        yard = _rel(restate(c, us, vs, w0), ref)
-        bound = R.sum_bound(T + p["extra"], restate(c, d(us), d(vs), d(w0), absolute=True))
-        rb = yb = bb = None
-        if c["bias"]:
-            b0 = None if db0 is None else db0[s]
-            rb = R.colsum(d(us), d(b0))
-            yb = _rel(R.colsum(us, b0), rb)
-            bb = R.sum_bound(WC.pixels(c) + p["bias_extra"], R.colsum(d(us), d(b0), absolute=True))
-        out.append((ref, yard, bound, rb, yb, bb))
-    return out
-
-
-_REF = {}
-
-
-def reference(c):
-    if c["name"] not in _REF:
-        _REF[c["name"]] = reference_of(c, *WC.inputs(c))
-    return _REF[c["name"]]
 
 
 # ---- one case on carved buffers --------------------------------------------------------------------------------------------------------------

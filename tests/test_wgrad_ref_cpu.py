@@ -5,30 +5,20 @@ every regime of the dispatch code and every reduce variant is reached, impulse i
 need no GPU - give the workspace and therefore the split every case claims) and the sensitivity of the table: plausible kernel flaws, seeded into
 copies of the restatements that live in this file only, each move some case past a condition the GPU file holds it to by SENSITIVITY_FACTOR or
 more, or flip an exact comparison."""
-import importlib.util
-import os
-
 import pytest
 import torch
 import torch.nn.functional as F
 
 from oracle import conv_ref as R
 from oracle import wgrad_cases as WC
+import _wgrad_checks as G  # the references and bounds the GPU file holds the device to
+from _fp64 import _ratio, cpu_threads
 
 SENSITIVITY_FACTOR = 10.0
 TOL = 1e-10
 
 
-def _gpu_module():
-    """the GPU test's references and bounds (importing it needs no GPU)"""
-    spec = importlib.util.spec_from_file_location("wgrad_fp64_gpu_refs", os.path.join(os.path.dirname(os.path.abspath(__file__)), "test_wgrad_fp64_gpu.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-G = _gpu_module()
-G.F._cpu_threads()
+cpu_threads()
 ENGINES = ["mfma", "tapn", "narrow", "c1rows", "c1valu", "direct", "wino", "s2"]
 
 
@@ -76,12 +66,12 @@ def test_restatements_match_autograd_and_bound_their_own_fp32_error(engine):
             if engine in ("wino", "s2"):
                 _close(G.restate(c, d(us), d(vs), d(w0)), ref, c["name"] + " Winograd form")
             # A dominates the fp32 restatement's own error: the bound is sound for the reference alone
-            r = G._ratio(G.restate(c, us, vs, w0), ref, bound)
+            r = _ratio(G.restate(c, us, vs, w0), ref, bound)
             assert r <= 1.0, "%s: the fp32 restatement is %.3g x the bound off" % (c["name"], r)
             assert yard > 0
             if rb is not None:
                 b0 = None if db0 is None else db0[s]
-                assert G._ratio(R.colsum(us, b0), rb, bb) <= 1.0 and yb > 0, c["name"]
+                assert _ratio(R.colsum(us, b0), rb, bb) <= 1.0 and yb > 0, c["name"]
     assert checked >= 3, engine
 
 
@@ -318,9 +308,9 @@ def test_every_seeded_flaw_moves_a_case_past_its_bound():
         c = WC.BY_NAME[name]
         u, v, dw0, _ = (None if t is None else t.double() for t in WC.inputs(c))
         ref, yard, bound = G.reference(c)[s][:3]
-        with_flaw = G._ratio(flawed(c, u, v, dw0, flaw, s), ref, bound)
+        with_flaw = _ratio(flawed(c, u, v, dw0, flaw, s), ref, bound)
         clean = "no_flaw" if c["engine"] not in ("wino", "s2") else None
-        without = G._ratio(flawed(c, u, v, dw0, clean, s), ref, bound) if clean else G._ratio(_wino_copy(c, *WC.operands(c, u, v, s), None) + (0 if dw0 is None else dw0[s]), ref, bound)
+        without = _ratio(flawed(c, u, v, dw0, clean, s), ref, bound) if clean else _ratio(_wino_copy(c, *WC.operands(c, u, v, s), None) + (0 if dw0 is None else dw0[s]), ref, bound)
         print("%-40s moves %-26s to %.3g x the bound (without the flaw: %.3g)" % (flaw, name, with_flaw, without))
         assert without <= 1.0, "%s: the copy without the flaw is off the reference" % flaw
         assert with_flaw >= SENSITIVITY_FACTOR, "%s: moves its case by only %.3g x the bound" % (flaw, with_flaw)
@@ -333,8 +323,8 @@ def test_bias_sum_missing_one_lane_half_is_caught():
     u, _, _, db0 = (None if t is None else t.double() for t in WC.inputs(c))
     rb, yb, bb = G.reference(c)[0][3:]
     half = R.colsum(u[0][:, :, 0::2], None if db0 is None else db0[0])
-    assert G._ratio(R.colsum(u[0], None if db0 is None else db0[0]), rb, bb) <= 1.0
-    assert G._ratio(half, rb, bb) >= SENSITIVITY_FACTOR
+    assert _ratio(R.colsum(u[0], None if db0 is None else db0[0]), rb, bb) <= 1.0
+    assert _ratio(half, rb, bb) >= SENSITIVITY_FACTOR
 
 
 def test_impulse_comparison_flips_under_index_flaws():

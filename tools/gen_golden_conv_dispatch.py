@@ -13,7 +13,6 @@ depend on what ran before). A scratch request is ["workspace" | "defer_workspace
 """
 import ctypes
 import lzma
-import importlib.util
 import json
 import os
 import sys
@@ -22,6 +21,9 @@ import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if os.path.join(ROOT, "tests") not in sys.path:
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+import _ops_cases as T  # noqa: E402  (the geometries tests/test_ops_gpu.py runs)
 GOLDEN = os.path.join(ROOT, "tests", "golden", "conv_dispatch.json.xz")
 MAIN, SIDE = 0x5151515100, 0x5252525200        # stand-ins for the raw stream handles
 
@@ -29,17 +31,9 @@ TUNINGS = {"wino0": {"HWG_WINO": "0"}, "wino2": {"HWG_WINO": "2", "HWG_WINO_S2":
 FLAGS = {"plain": (False, False), "defer": (True, False), "side": (False, True), "defer_side": (True, True)}       # (DEFER_REDUCE, SIDE_WGRAD)
 
 
-def _test_cases():
-    spec = importlib.util.spec_from_file_location("ops_gpu_cases", os.path.join(ROOT, "tests", "test_ops_gpu.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
 def cases():
     """[(name, variant, kind, geometry)]: variant = param (leaf parameters with bias) | nonleaf | nobias | sn_defer; kind = conv | conv1d |
     linear | linear_wgrad"""
-    T = _test_cases()
     out = [(c[0], "param", "conv", c[1:]) for c in T.CONV_CASES + T.RANDOM_CONV_CASES]
     # 4x4 stride-2 pad-0 layers: the two-tap Winograd entries (no CONV_CASES row reaches them)
     for (N, H, W, C, K, _env) in T.WINO_S2_CASES:

@@ -106,7 +106,7 @@ def time_action(args, say):
     import torch
     import generate as cli
     from oracle import collate_items
-    from test_reference_checkpoint_cpu import unpack
+    from _reference_checkpoint import unpack
     from handwriting_line_generation_amd import ops
     from handwriting_line_generation_amd.harness import CHAR_FILES
     from handwriting_line_generation_amd.logger import load_checkpoint

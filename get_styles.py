@@ -1,10 +1,10 @@
 #!/usr/bin/env python
-"""python get_styles.py -c checkpoint.pth -d out_dir [-g gpu] [-b batch] [-f config.json] [-a k=v,...] [-T] [--cer] [--writer-id] [--distances]
+"""python get_styles.py -c checkpoint.pth -d out_dir [-g gpu] [-b batch] [-f config.json] [-a k=v,...] [-T] [--cer [--beam K]] [--writer-id] [--distances]
 The reference's get_styles.py: the style vector of every line of the training and validation splits (with -T: of the test split), written
 as <savedir>/train_styles_<iteration>.pkl and val_styles_<iteration>.pkl (test_styles_<iteration>.pkl): {"styles": float32 [n, style_dim],
 "authors": array [n]} - what `generate.py -s` samples from. Only the model is built (no trainer, no optimizer). With --cer the recogniser's
 error rates on the real lines and on the same texts rendered in their own extracted style are counted on the GPU on the way and written to
-<split>_cer_<iteration>.json. With --writer-id the written styles are scored for writer retrieval (evaluate.writer_id with dedupe: top-1 / 5 / 20
+<split>_cer_<iteration>.json; --beam K adds the rates of the CTC prefix beam search's text (width K) to that file. With --writer-id the written styles are scored for writer retrieval (evaluate.writer_id with dedupe: top-1 / 5 / 20
 under L1 and squared L2, what eval_writer_id.py --dedupe prints) into <split>_writer_id_<iteration>.json. With --distances their same-writer and
 different-writer distances (evaluate.style_distances with dedupe, without the writer x writer matrices: pairs, mean, std and the two histograms,
 what play_styles.py --dedupe prints) go into <split>_distances_<iteration>.json."""
@@ -30,6 +30,9 @@ def parse_args(argv=None):
     ap.add_argument("-T", "--test", action="store_true", help="the test split (default: train and valid)")
     ap.add_argument("-S", "--transformstyle", action="store_true", help="(not built)")
     ap.add_argument("--cer", action="store_true", help="also score the recogniser on real and regenerated lines: <split>_cer_<iteration>.json")
+    ap.add_argument("--beam", type=int, default=0, metavar="K",
+                    help="with --cer: also decode by CTC prefix beam search of width K (1..32 on the GPU): beam, cer_real_beam, wer_real_beam, "
+                         "cer_gen_beam, wer_gen_beam in the same file")
     ap.add_argument("--writer-id", dest="writer_id", action="store_true",
                     help="also score the written styles for writer retrieval: <split>_writer_id_<iteration>.json")
     ap.add_argument("--distances", action="store_true",
@@ -50,6 +53,10 @@ def main(argv=None):
         raise SystemExit("get_styles.py: must provide a directory to write to (with -d)")
     if args.batchsize is not None and args.batchsize < 1:
         raise SystemExit("get_styles.py: -b must be at least 1")
+    if args.beam < 0:
+        raise SystemExit("get_styles.py: --beam must be at least 1")
+    if args.beam and not args.cer:
+        raise SystemExit("get_styles.py: --beam decodes what --cer scores; pass --cer with it")
 
     import numpy as np
     import torch
@@ -90,7 +97,7 @@ def main(argv=None):
             print("%s: no lines" % name, flush=True)
             continue
         t0 = time.time()
-        result = evaluate.eval_split(model, config, loader, gpu) if args.cer else evaluate.extract_styles(model, loader, gpu)
+        result = evaluate.eval_split(model, config, loader, gpu, beam=args.beam) if args.cer else evaluate.extract_styles(model, loader, gpu)
         torch.cuda.synchronize()
         dt = time.time() - t0
         loc = os.path.join(args.savedir, "%s_styles_%s.pkl" % (name, iteration))
@@ -103,6 +110,9 @@ def main(argv=None):
                 json.dump({k: v for k, v in result.items() if k not in ("styles", "authors")}, f)
             print("saved %s  cer_real %.4f  wer_real %.4f  cer_gen %.4f  wer_gen %.4f" % (
                 loc, result["cer_real"], result["wer_real"], result["cer_gen"], result["wer_gen"]), flush=True)
+            if args.beam:
+                print("  beam %d  cer_real %.4f  wer_real %.4f  cer_gen %.4f  wer_gen %.4f" % (
+                    result["beam"], result["cer_real_beam"], result["wer_real_beam"], result["cer_gen_beam"], result["wer_gen_beam"]), flush=True)
         if args.writer_id:
             loc = os.path.join(args.savedir, "%s_writer_id_%s.json" % (name, iteration))
             scores = evaluate.writer_id(result["styles"], result["authors"], gpu, dedupe=True)

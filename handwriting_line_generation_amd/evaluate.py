@@ -101,22 +101,25 @@ def _char_set(config):
         return {int(k): v for k, v in json.load(f)["idx_to_char"].items()}
 
 
-def eval_split(model, config, loader, gpu):
+def eval_split(model, config, loader, gpu, beam=0):
     """extract_styles, and on the way the recogniser's error rates on every real line and on the same text rendered in the line's own
     extracted style, counted on the device (ops.ctc_error_rates; a batch's counts are read while the next batch runs). Adds to
     extract_styles' result: "lines", per-line lists "cer_real_lines" / "wer_real_lines" / "cer_gen_lines" / "wer_gen_lines" and their means
-    over the lines "cer_real" / "wer_real" / "cer_gen" / "wer_gen"."""
+    over the lines "cer_real" / "wer_real" / "cer_gen" / "wer_gen". beam > 0: the same predictions are also decoded by CTC prefix beam
+    search of that width (ops.ctc_beam_error_rates) - "beam" and the same eight entries with "_beam" after the name, next to the
+    unchanged greedy ones."""
     idx_to_char = _char_set(config)
     casesensitive = config.get("trainer", {}).get("casesensitive", True)
     was_training = model.training
     model.eval()
     fetches, authors, handles = [], [], []
     per_line = {"cer_real": [], "wer_real": [], "cer_gen": [], "wer_gen": []}
+    if beam:
+        per_line.update({"cer_real_beam": [], "wer_real_beam": [], "cer_gen_beam": [], "wer_gen_beam": []})
 
     def settle(keep):
         while len(handles) > keep:
-            real, gen = handles.pop(0)
-            for name, handle in (("real", real), ("gen", gen)):
+            for name, handle in zip(("real", "gen", "real_beam", "gen_beam"), handles.pop(0)):
                 cers, wers, _ = handle.result()
                 per_line["cer_" + name] += cers
                 per_line["wer_" + name] += wers
@@ -129,8 +132,12 @@ def eval_split(model, config, loader, gpu):
                 model.pred = pred
                 style = model.extract_style(image, label, inst.get("a_batch_size"))
                 gen_pred = model.hwr(model(label, inst["label_lengths"], style), None)
-                handles.append((ops.ctc_error_rates(pred, inst["gt"], idx_to_char, casesensitive),
-                                ops.ctc_error_rates(gen_pred, inst["gt"], idx_to_char, casesensitive)))
+                batch = (ops.ctc_error_rates(pred, inst["gt"], idx_to_char, casesensitive),
+                         ops.ctc_error_rates(gen_pred, inst["gt"], idx_to_char, casesensitive))
+                if beam:
+                    batch += (ops.ctc_beam_error_rates(pred, inst["gt"], idx_to_char, casesensitive, beam),
+                              ops.ctc_beam_error_rates(gen_pred, inst["gt"], idx_to_char, casesensitive, beam))
+                handles.append(batch)
                 fetches.append(ops.AsyncFetch(style))
                 authors += list(inst["author"])
                 _reset(model)
@@ -142,6 +149,8 @@ def eval_split(model, config, loader, gpu):
             model.train()
     out = _styles_result(fetches, authors, model.style_dim)
     out["lines"] = len(per_line["cer_real"])
+    if beam:
+        out["beam"] = int(beam)
     for name, values in per_line.items():
         total = 0
         for v in values:

@@ -283,7 +283,11 @@ def begin(config, instance, trainer, metrics, outDir=None, startIndex=None, toEv
     if "pred" in out:
         if hook is not None:
             hook("pred", list(instance["name"]), {"pred": out["pred"], "gt": list(instance["gt"])})
-        p.rates = ops.ctc_error_rates(out["pred"], instance["gt"], trainer.idx_to_char, getattr(trainer, "casesensitive", True))
+        if config.get("beam"):                 # `-a beam=K`: the text, and with it every rate below, is the prefix beam search's
+            p.rates = ops.ctc_beam_error_rates(out["pred"], instance["gt"], trainer.idx_to_char, getattr(trainer, "casesensitive", True),
+                                               beam=config["beam"])
+        else:
+            p.rates = ops.ctc_error_rates(out["pred"], instance["gt"], trainer.idx_to_char, getattr(trainer, "casesensitive", True))
         if p.aligned is None:
             p.aligned = ops.dtw_align_async(out["pred"].detach().contiguous(), instance["label"])
     return p

@@ -2992,7 +2992,6 @@ def ctc_error_rates(pred, gt, idx_to_char, casesensitive=True):
     device: -> ErrorRatesPending. One upload (class table, reference offsets and code points), two launches, one asynchronous fetch. Where
     the device cannot give string_utils.cer / wer's values - a character set class_code_table refuses, or a size beyond the kernel's limits -
     the batch takes the host path: same values, said once on stderr."""
-    import numpy as np
     from .utils import string_utils
     global error_rate_fallbacks, _error_rate_fallback_said
     if pred.dim() != 3 or not pred.is_cuda or pred.dtype != torch.float32:
@@ -3013,19 +3012,114 @@ def ctc_error_rates(pred, gt, idx_to_char, casesensitive=True):
                 "T=%d C=%d longest reference %d is beyond the kernel's limits (%d, %d, %d)" % (T, C, longest, ER_MAX_T, ER_MAX_C, ER_MAX_REF)
             print("ctc_error_rates: %s; such batches are scored on the host" % why, file=sys.stderr)
         return ErrorRatesPending(None, T, refs, idx_to_char, done=host_error_rates(pred.cpu().numpy(), gt, idx_to_char, casesensitive))
+    packed_d = _upload_refs(table, refs, pred.device)
+    out = torch.empty((8 * B + B * T,), dtype=torch.int32, device=pred.device)
+    L.call("hwg_ctc_error_rates", pred, T, B, C, packed_d, packed_d[C + B + 1:], packed_d[C:C + B + 1], longest, out, _stream())
+    return ErrorRatesPending(AsyncFetch(out), T, refs, idx_to_char)
+
+
+def _upload_refs(table, refs, device):
+    """class table [C], reference offsets [B + 1] and the references' code points (at least one int) as one int32 upload"""
+    import numpy as np
+    C, B = len(table), len(refs)
     offsets = np.zeros(B + 1, dtype=np.int32)
     np.cumsum([len(r) for r in refs], out=offsets[1:])
     total = int(offsets[B])
-    packed = np.empty(C + B + 1 + max(total, 1), dtype=np.int32)          # class table, offsets, code points: one upload
+    packed = np.empty(C + B + 1 + max(total, 1), dtype=np.int32)
     packed[:C] = table
     packed[C:C + B + 1] = offsets
     packed[C + B + 1:] = 0
     if total:
         packed[C + B + 1:C + B + 1 + total] = np.fromiter((c for r in refs for c in r), dtype=np.int32, count=total)
-    packed_d = h2d(packed, pred.device)
-    out = torch.empty((8 * B + B * T,), dtype=torch.int32, device=pred.device)
-    L.call("hwg_ctc_error_rates", pred, T, B, C, packed_d, packed_d[C + B + 1:], packed_d[C:C + B + 1], longest, out, _stream())
-    return ErrorRatesPending(AsyncFetch(out), T, refs, idx_to_char)
+    return h2d(packed, device)
+
+
+# ----------------------------------------------------------------------------------------------
+# the same error rates over the CTC prefix beam search's text (csrc/ctc_beam.hip)
+# ----------------------------------------------------------------------------------------------
+CB_MAX_BEAM, CB_MAX_T, CB_MAX_C = 32, 2048, 1024         # the limits hwg_ctc_beam_error_rates checks (the reference limit is ER_MAX_REF)
+beam_fallbacks = 0                                       # batches that took the host path (tests read it)
+_beam_fallback_said = False
+
+
+class BeamErrorRatesPending(ErrorRatesPending):
+    """ErrorRatesPending of the beam text; `.scores()` -> fp32 numpy [B, beam]: the final totals, descending, -inf padded"""
+
+    def __init__(self, fetch, T, refs, idx_to_char, beam, done=None, scores=None):
+        ErrorRatesPending.__init__(self, fetch, T, refs, idx_to_char, done)
+        self.beam, self._scores = beam, scores
+
+    def _host(self):
+        return self.fetch.get().numpy()[:len(self.refs) * (8 + self.T)]
+
+    def counts(self):
+        if self.fetch is None:
+            return None
+        host, B = self._host(), len(self.refs)
+        return host[:8 * B].reshape(B, 8), host[8 * B:].reshape(B, self.T)
+
+    def scores(self):
+        if self._scores is None:
+            import numpy as np
+            B = len(self.refs)
+            self._scores = self.fetch.get().numpy()[B * (8 + self.T):].view(np.float32).reshape(B, self.beam).copy()
+        return self._scores
+
+
+def host_beam_error_rates(pred, gt, idx_to_char, casesensitive=True, beam=16):
+    """the host path of ctc_beam_error_rates on a [T,B,C] numpy array -> ((cer_list, wer_list, pred_strs), scores fp32 [B, beam])"""
+    import numpy as np
+    from .utils import string_utils
+    cers, wers, strs = [], [], []
+    scores = np.empty((len(gt), beam), dtype=np.float32)
+    for i, gt_line in enumerate(gt):
+        ids, _, totals = string_utils.prefix_beam_decode(pred[:, i], beam)
+        s = string_utils.label2str_single(ids, idx_to_char, False)
+        cers.append(string_utils.cer(gt_line, s, casesensitive))
+        wers.append(string_utils.wer(gt_line, s, casesensitive))
+        strs.append(s)
+        scores[i] = totals
+    return (cers, wers, strs), scores
+
+
+def ctc_beam_error_rates(pred, gt, idx_to_char, casesensitive=True, beam=16):
+    """CTC prefix beam search (width `beam`) over the recogniser's output `pred` [T,B,C] (device, fp32, read as log-probabilities as they
+    stand) and CER / WER of every line's most probable text against `gt`, on the device: -> BeamErrorRatesPending. One upload, two
+    launches, one asynchronous fetch (counts, decoded ids and scores in one buffer); the workspace comes from the caching allocator.
+    Where the device cannot serve - a character set class_code_table refuses, or a size beyond the kernel's limits - the batch is decoded
+    and scored on the host (string_utils.prefix_beam_decode, fp64), said once on stderr."""
+    from .utils import string_utils
+    global beam_fallbacks, _beam_fallback_said
+    if not torch.is_tensor(pred) or pred.dim() != 3 or not pred.is_cuda or pred.dtype != torch.float32:
+        raise L.HwgError("ctc_beam_error_rates: pred must be a [T,B,C] fp32 device tensor, got %s %s" % (
+            tuple(pred.shape) if torch.is_tensor(pred) else type(pred), getattr(pred, "dtype", None)))
+    T, B, C = pred.shape
+    if T < 1 or B < 1 or C < 2 or len(gt) != B:
+        raise L.HwgError("ctc_beam_error_rates: %d texts for pred %s" % (len(gt), tuple(pred.shape)))
+    beam = int(beam)
+    if beam < 1:
+        raise L.HwgError("ctc_beam_error_rates: a beam of %d" % beam)
+    pred = pred.detach().contiguous()
+    table = string_utils.class_code_table(idx_to_char, C, casesensitive)
+    refs = [string_utils.normalise_ref(g, casesensitive) for g in gt]
+    longest = max(len(r) for r in refs)
+    if table is None or beam > CB_MAX_BEAM or T > CB_MAX_T or C > CB_MAX_C or longest > ER_MAX_REF:
+        beam_fallbacks += 1
+        if not _beam_fallback_said:
+            _beam_fallback_said = True
+            import sys
+            why = "the character set does not compare class by class" if table is None else \
+                "beam=%d T=%d C=%d longest reference %d is beyond the kernel's limits (%d, %d, %d, %d)" % (
+                    beam, T, C, longest, CB_MAX_BEAM, CB_MAX_T, CB_MAX_C, ER_MAX_REF)
+            print("ctc_beam_error_rates: %s; such batches are decoded and scored on the host" % why, file=sys.stderr)
+        done, scores = host_beam_error_rates(pred.cpu().numpy(), gt, idx_to_char, casesensitive, beam)
+        return BeamErrorRatesPending(None, T, refs, idx_to_char, beam, done=done, scores=scores)
+    packed_d = _upload_refs(table, refs, pred.device)
+    out = torch.empty((8 * B + B * T + B * beam,), dtype=torch.int32, device=pred.device)      # the scores ride behind the ids: one fetch
+    ws = torch.empty(L.query("hwg_ctc_beam_workspace", T, B, C, beam), dtype=torch.uint8, device=pred.device)
+    L.call("hwg_ctc_beam_error_rates", pred, T, B, C, beam, packed_d, packed_d[C + B + 1:], packed_d[C:C + B + 1], longest, out,
+           out[8 * B + B * T:], ws, ws.numel(), _stream())
+    return BeamErrorRatesPending(AsyncFetch(out), T, refs, idx_to_char, beam)
 
 
 # ----------------------------------------------------------------------------------------------

@@ -53,6 +53,62 @@ def wer(r, h, casesensitive=True):
     return _levenshtein(r, h) / float(len(r))
 
 
+def prefix_beam_decode(lp, beam):
+    """CTC prefix beam search over [T, C] log-probabilities as they stand (class 0 the blank, a NaN reads as -inf), in fp64: the host side
+    and definition of ops.ctc_beam_error_rates (csrc/ctc_beam.hip). -> (ids, score, totals): the prefix of largest total (pb (+) pnb, (+) =
+    log-add-exp), that total (-inf with an empty beam, ids [] then), and all final totals, descending, padded with -inf to `beam`.
+    Of exactly equal totals the candidate of the earlier beam slot wins, within a slot the prefix itself before its extensions in ascending
+    class order - the kernel's rule."""
+    lp = np.array(lp, dtype=np.float64)
+    lp[np.isnan(lp)] = -np.inf
+    T, C = lp.shape
+    ninf = -np.inf
+    lse = np.logaddexp
+    slots = [((), 0.0, ninf)]                            # (prefix, pb, pnb), best first
+    with np.errstate(invalid="ignore"):
+        for t in range(T):
+            row = lp[t]
+            new = {}                                     # prefix -> [pb, pnb, candidate index]
+            for j, (pre, pb, pnb) in enumerate(slots):
+                new[pre] = [ninf, ninf, j * C]
+            for j, (pre, pb, pnb) in enumerate(slots):
+                tot = lse(pb, pnb)
+                e = new[pre]
+                e[0] = lse(e[0], row[0] + tot)
+                if pre:
+                    e[1] = lse(e[1], row[pre[-1]] + pnb)
+                for c in range(1, C):
+                    v = row[c] + (pb if pre and c == pre[-1] else tot)
+                    if v == ninf:
+                        continue
+                    e = new.get(pre + (c,))
+                    if e is None:
+                        new[pre + (c,)] = [ninf, v, j * C + c]
+                    else:
+                        e[1] = lse(e[1], v)
+            cand = [(lse(pb, pnb), idx, pre, pb, pnb) for pre, (pb, pnb, idx) in new.items()]
+            cand = sorted((x for x in cand if x[0] > ninf), key=lambda x: (-x[0], x[1]))[:beam]
+            slots = [(pre, pb, pnb) for _, _, pre, pb, pnb in cand]
+    totals = np.full(beam, ninf)
+    totals[:len(slots)] = [lse(pb, pnb) for _, pb, pnb in slots]
+    if not slots:
+        return [], ninf, totals
+    return list(slots[0][0]), float(totals[0]), totals
+
+
+def shortest_ctc_path(ids, T):
+    """the shortest CTC alignment of the class sequence `ids`: one blank between equal neighbours, zero padded to T frames (what the beam
+    kernel hands to the greedy collapse, which returns exactly `ids`); ValueError when it does not fit"""
+    path = []
+    for i, c in enumerate(ids):
+        if i and c == ids[i - 1]:
+            path.append(0)
+        path.append(int(c))
+    if len(path) > T:
+        raise ValueError("a text of %d classes with %d doubled neighbours has no alignment of %d frames" % (len(ids), len(path) - len(ids), T))
+    return path + [0] * (T - len(path))
+
+
 # ---- the host side of ops.ctc_error_rates: cer / wer above, split into what the host prepares, what the device counts and the division ----
 SPACE = 32
 

@@ -735,6 +735,30 @@ int hwg_ctc_error_rates(const float* pred, int T, int B, int C, const int* class
                         int max_ref_len, int* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * CTC prefix beam search in front of the same counts (csrc/ctc_beam.hip; the reference decodes greedily only - this is the standard
+ * decoder of a CTC-trained model, which sums the alignments of a text instead of scoring the single best one).
+ * pred [T][B][C] fp32, read as log-probabilities as they stand (no renormalisation; class 0 the blank; a NaN reads as -inf). Per line a
+ * beam of at most `beam` prefixes (sequences of classes 1 .. C-1), each with pb / pnb, the log-mass of its alignments ending in a blank /
+ * in a non-blank, tot = pb (+) pnb with (+) = log-add-exp; start {(): pb 0, pnb -inf}. Frame t, for every beam prefix l, into a fresh table:
+ *   new[l].pb (+)= lp[t][0] + tot(l);   l not empty: new[l].pnb (+)= lp[t][last(l)] + pnb(l);
+ *   every c >= 1: new[l+c].pnb (+)= lp[t][c] + (pb(l) if c == last(l) else tot(l))
+ * (l+c may itself be in the beam: one entry - prefixes are equal when their class sequences are, decided on the trie node, never by a
+ * hash alone), then the `beam` entries of largest tot; a tot of -inf never enters. Of exactly equal totals the candidate of the earlier
+ * (better) beam slot wins, within a slot the prefix itself before its extensions in ascending class order. Fixed summation orders: two
+ * runs give the same bits, a line's result depends neither on B nor on the other lines.
+ * out: the layout of hwg_ctc_error_rates - per line stats[8], then decoded [B][T]: the prefix of largest final tot (the empty text when
+ * the beam is empty), row b: stats[0] ids, then zeros; the stats are those of that text. scores fp32 [B][beam]: the final totals,
+ * descending, padded with -inf. ws: hwg_ctc_beam_workspace(T, B, C, beam) bytes, 8-byte aligned, contents irrelevant; HWG_ERR_WORKSPACE
+ * when it is NULL or smaller. Every element of out and scores is written.
+ * Limits, checked here before any launch: 1 <= beam <= 32, T <= 2048, C <= 1024, max_ref_len <= 2047; pred, out, scores 4-byte aligned.
+ * Two launches: one workgroup per line with the frame loop inside, then the line kernel of hwg_ctc_error_rates on the best prefix
+ * written as its shortest CTC path.
+ * ------------------------------------------------------------------------------------------ */
+size_t hwg_ctc_beam_workspace(int T, int B, int C, int beam);
+int hwg_ctc_beam_error_rates(const float* pred, int T, int B, int C, int beam, const int* class_code, const int* ref_codes,
+                             const int* ref_offsets, int max_ref_len, int* out, float* scores, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Writer retrieval over style vectors (eval_writer_id.py:15-29 topN over the :70-81 all-pairs l1 / l2 / gt matrices - there nested
  * Python loops, two N x N fp64 matrices and a Python sort per row).
  * styles [N][D] fp32, author_id [N] int32 (equal ids = same writer); metric 0: sum |a - b|, 1: sum (a - b)^2 (no root), both one fp32

@@ -9,7 +9,8 @@ Without -d the whole validation split is scored. Everything per pixel and per ch
 
 -a adds config keys: save_preds=<csv> (name, gt, pred, cer of the training batches), save_style=<path> with saveStyleEvery=<batches>
 ({"styles", "authors"} pickles <path>.<volume> and val_<path>.<volume>), by_author (CER lists per writer), cer_thresh=<x> (pictures only of
-lines at or above it, named '<cer>_<line>_recon.png'), skip_valid, skip_train, startBatch=<k>.
+lines at or above it, named '<cer>_<line>_recon.png'), skip_valid, skip_train, startBatch=<k>, beam=<K> (the `pred:` text and every
+rate from it come from a CTC prefix beam search of width K on the GPU instead of the greedy decode; a header line says so).
 Not built, refused with the reason: the config keys of REFUSED_KEYS and `-e spaced|spacing|mask` and the mask pictures."""
 import argparse
 import csv
@@ -139,6 +140,10 @@ def prepare_config(config, args):
     config["cuda"], config["gpu"] = True, 0 if args.gpu is None else args.gpu
     apply_addtoconfig(config, args.adds)
     check_config(config)
+    if "beam" in config:
+        if isinstance(config["beam"], bool) or not isinstance(config["beam"], int) or config["beam"] < 1:
+            raise SystemExit("new_eval.py: beam=K needs a width K >= 1, got %r" % (config["beam"],))
+        print("decoding: CTC prefix beam search, beam {} (pred, CER / WER, by_author, cer_thresh and save_preds use its text)".format(config["beam"]))
     dl = config["data_loader"]
     val = config.setdefault("validation", {})
     dl["shuffle"] = val["shuffle"] = bool(args.shuffle)

@@ -2553,6 +2553,96 @@ def lines_from_u8(pixels, offsets, widths, select, real=None, out=None, height=6
     return out.view(-1)[:B * H * W].view(B, 1, H, W)
 
 
+# ----------------------------------------------------------------------------------------------
+# line images of any height fitted to the recognisers' height, PIL's bytes (csrc/fit_lines.hip)
+# ----------------------------------------------------------------------------------------------
+FIT_MAX_IN_H, FIT_MAX_H, FIT_MAX_W, FIT_MAX_B = 1024, 1024, 1 << 20, 65535      # the limits hwg_fit_lines checks
+fit_fallbacks = 0                                        # lines (or, for a batch beyond the limits, batches) fitted on the host (tests read it)
+_fit_fallback_said = False
+
+
+def _fit_said(why):
+    global _fit_fallback_said
+    if not _fit_fallback_said:
+        _fit_fallback_said = True
+        import sys
+        print("fit_lines: %s; such lines are fitted on the host" % why, file=sys.stderr)
+
+
+def fit_lines(images, height=64, W=None, out=None, device=None):
+    """Grey line pictures of any height and width - a list of 2-D uint8 numpy arrays - resized to `height` rows and the width the loaders'
+    `_resize` gives them (data.fit_tables.fitted_width), bicubic with PIL's bytes, mapped to 1 - p / 128 and collated padded with -1:
+    -> (batch [B,1,H,W] fp32 device tensor, widths list). One upload of the pixels, one of the tables (per-line entries and the coefficient
+    tables of data.fit_tables, one per distinct (in, out) pair of the batch), one launch (hwg_fit_lines). W: the batch width, a multiple of 4
+    not below the widest fitted line (default: that width rounded up to a multiple of 4). `out`: a contiguous 16-byte aligned fp32 device
+    buffer of at least B * H * W elements to write into. `device`: out's, else the current one. A picture beyond the kernel's limits
+    (taller than FIT_MAX_IN_H, wider than FIT_MAX_W) is fitted on the host with `_resize` and goes through the launch as it is (both
+    passes skipped); a batch beyond them (H, W, B) is fitted and collated on the host and uploaded. The values are the same; it is said
+    once on stderr and counted in ops.fit_fallbacks."""
+    import numpy as np
+    from .data import fit_tables as FT
+    from .data.author_hw_dataset import _resize
+    global fit_fallbacks
+    H = int(height)
+    if H < 1:
+        raise L.HwgError("fit_lines: line height %d" % H)
+    images = list(images)
+    if not images:
+        raise L.HwgError("fit_lines: no images")
+    for i, im in enumerate(images):
+        if not isinstance(im, np.ndarray) or im.dtype != np.uint8 or im.ndim != 2 or im.shape[0] < 1 or im.shape[1] < 1:
+            raise L.HwgError("fit_lines: image %d must be a non-empty 2-D uint8 numpy array, got %s %s" % (
+                i, getattr(im, "shape", type(im)), getattr(im, "dtype", None)))
+    B = len(images)
+    widths = [FT.fitted_width(im.shape[0], im.shape[1], H) for im in images]
+    Wmin = -(-max(widths) // 4) * 4
+    if W is None:
+        W = Wmin
+    W = int(W)
+    if W % 4 or W < max(widths):
+        raise L.HwgError("fit_lines: batch width %d must be a multiple of 4 and at least the widest fitted line (%d)" % (W, max(widths)))
+    if device is None:
+        device = out.device if torch.is_tensor(out) else torch.device("cuda", torch.cuda.current_device())
+    if out is None:
+        out = torch.empty((B, 1, H, W), dtype=torch.float32, device=device)
+    elif (not torch.is_tensor(out) or not out.is_cuda or out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < B * H * W
+          or out.data_ptr() % 16):
+        raise L.HwgError("fit_lines: out must be a contiguous 16-byte aligned fp32 device buffer of at least %d elements" % (B * H * W))
+    batch = out.view(-1)[:B * H * W].view(B, 1, H, W)
+
+    def on_host(im):
+        fitted = im if im.shape[0] == H else _resize(im, float(H) / im.shape[0])
+        assert fitted.shape[0] == H, (im.shape, fitted.shape)
+        return np.ascontiguousarray(fitted)
+    if H > FIT_MAX_H or W > FIT_MAX_W or B > FIT_MAX_B:
+        fit_fallbacks += 1
+        _fit_said("H=%d W=%d B=%d is beyond the kernel's limits (%d, %d, %d)" % (H, W, B, FIT_MAX_H, FIT_MAX_W, FIT_MAX_B))
+        host = np.full((B, 1, H, W), -1.0, dtype=np.float32)
+        for b, im in enumerate(images):
+            fitted = on_host(im)
+            host[b, 0, :, :fitted.shape[1]] = np.float32(1.0) - fitted.astype(np.float32) / np.float32(128.0)
+        batch.copy_(h2d(host, device))
+        return batch, widths
+    for b, im in enumerate(images):
+        if im.shape[0] > FIT_MAX_IN_H or im.shape[1] > FIT_MAX_W:
+            fit_fallbacks += 1
+            _fit_said("a picture of %d x %d is beyond the kernel's limits (%d rows, %d columns)" % (im.shape[0], im.shape[1], FIT_MAX_IN_H, FIT_MAX_W))
+            images[b] = on_host(im)
+            assert images[b].shape[1] == widths[b], (im.shape, images[b].shape, widths[b])
+    # the tables: lines [B][10] int64 first, then one coefficient block per distinct (in, out) pair - one upload
+    lines, coef = FT.batch_tables([im.shape for im in images], H, widths)
+    n = lines.size * 2
+    table = np.empty(n + coef.size, dtype=np.int32)
+    table[:n] = lines.reshape(-1).view(np.int32)
+    table[n:] = coef
+    pixels = np.concatenate([np.ascontiguousarray(im).reshape(-1) for im in images])
+    pixels_d = h2d(pixels, device)
+    table_d = h2d(table, device)
+    L.call("hwg_fit_lines", pixels_d, pixels.size, table_d, table_d[n:], coef.size, max(im.shape[0] for im in images), B, H, W,
+           batch, _stream())
+    return batch, widths
+
+
 def fg_masks(pixels, offsets, widths, height=64, out=None, want_thresholds=False):
     """Foreground masks of a ragged pool of grey lines (csrc/fg_mask.hip; the reference's cv2 Otsu threshold, inversion and dilation with the
     9 x 9 ellipse, datasets/author_hw_dataset.py:216-219) in one launch -> a uint8 pool of the same layout, 255 = foreground, 0 = not.

@@ -573,6 +573,35 @@ int hwg_lines_from_u8(const unsigned char* pixels, long long pixel_bytes, const 
                       const int* select, int min_select, const float* real, int Br, int Wr, int B, int H, int W, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Line images of any height fitted to the recognisers' height (csrc/fit_lines.hip; datasets/hw_dataset.py:128-131 resize + :157
+ * `1 - img / 128` + :21-67 collate, generate.py:655-663 - there per line on the host, through cv2.resize; this package's loaders use PIL,
+ * data/author_hw_dataset.py `_resize`, and PIL's bytes are what this entry reproduces).
+ * pixels: a ragged uint8 pool of grey pictures of differing heights and widths, any byte offsets. lines [B][10] int64 (device), per output
+ * row b: {byte offset of the row-major in_h x in_w picture, in_h, in_w, out_w, htab, hks, vtab, vks, order, 0}. coef (int32, device, coef_elems
+ * elements): the axis tables. The table of an axis of `in` pixels resized to `n` (n = out_w for the horizontal axis at element htab with
+ * ks = hks, n = H for the vertical one at vtab with ks = vks) is first[n], count[n], k[n][ks]: output index i reads the pixels first[i] ..
+ * first[i] + count[i] - 1 of its row / column with the 22-bit fixed-point weights k[i][0 .. count[i]). ks = 0: the pass is skipped, legal
+ * only where in == n. The tables are Pillow's (Resample.c, 8 bits per channel, bicubic a = -0.5), computed on the host in fp64
+ * (data/fit_tables.py resample_table).
+ * One launch writes every element of out [B][1][H][W] fp32: the horizontal pass first, acc = 2^21 + sum pixel * k in 32-bit integers,
+ * byte = clamp(acc >> 22, 0, 255), into an 8-bit intermediate that stays in LDS; then the vertical pass over those bytes in the same
+ * arithmetic; element = 1 - byte / 128 (exact in fp32) for columns < out_w, -1 (the padding constant) beyond. With the host's tables
+ * this is Image.resize((out_w, H), Image.BICUBIC) of an `L` image bit for bit. order = 1 runs the vertical pass first and the horizontal
+ * pass over its bytes, as Image.resize does for a picture more than 100 times as tall as wide that shrinks vertically; it is served for
+ * pictures of at most 64 columns. One workgroup owns 64 output columns of one line; a line's
+ * values depend on its own entry alone (no atomics, nothing shared between workgroups).
+ * Limits, checked here before the launch (HWG_ERR_ARG): no NULL; B, H, W, pixel_bytes, coef_elems, max_in_h > 0; B <= 65535, H <= 1024,
+ * W <= 2^20, W % 4 == 0; max_in_h - the tallest picture as the caller states it, it sizes the LDS - <= 1024; out and coef 16-byte
+ * aligned, lines 8-byte aligned. The tables are the caller's to check (device arrays: ops.fit_lines builds them on the host); the kernel
+ * turns a row whose entry is bad all the same into padding (the WHOLE row, every workgroup of it checks the whole entry) without reading
+ * anything through it: a picture that does not lie inside pixel_bytes (csrc/table_guard.h, any 64-bit offset), in_h outside
+ * [1, max_in_h], in_w outside [1, 2^20], out_w outside [1, W], ks outside [0, 2^16] or 0 where the sizes differ, an axis table that starts
+ * at no multiple of 4 or starts or ends outside coef_elems, a window with first < 0, count < 0, count > ks or first + count > in, an order other than 0 or 1, or 1 with in_w > 64.
+ * ------------------------------------------------------------------------------------------ */
+int hwg_fit_lines(const unsigned char* pixels, long long pixel_bytes, const long long* lines, const int* coef, long long coef_elems,
+                  int max_in_h, int B, int H, int W, float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Foreground masks of grey lines (csrc/fg_mask.hip; datasets/author_hw_dataset.py:197-220: cv2.threshold(BINARY + OTSU), 255 - that,
  * cv2.dilate with getStructuringElement(MORPH_ELLIPSE, (9, 9)) - there per line on the host).
  * pixels (uint8, pixel_bytes of them), offsets [B] int64 and widths [B] int32 on the device: line b is the row-major H x widths[b] picture

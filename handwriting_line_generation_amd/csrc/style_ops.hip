@@ -126,11 +126,12 @@ __global__ void segment_weighted_mean_bwd_kernel(const float* dout, const float*
     dv[i] = (ws != 0.f ? wgt[k] / ws : wgt[k]) * dout[(long long)b * C + c];
   }
 }
-// out[i] = exp(x[b_i][pos_i][cls_i])   (confidence of the recognised character)
-__global__ void gather_scores_kernel(const float* x, int Wx, int C, const int* idx_b, const int* idx_pos, const int* idx_cls, int n, float* out) {
+// out[i] = exp(x[b_i][pos_i][cls_i])   (confidence of the recognised character); 0 for an index outside the tensor, like gather_windows_kernel
+__global__ void gather_scores_kernel(const float* x, int B, int Wx, int C, const int* idx_b, const int* idx_pos, const int* idx_cls, int n, float* out) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= n) return;
-  out[k] = expf(x[((long long)idx_b[k] * Wx + idx_pos[k]) * C + idx_cls[k]]);
+  const int b = idx_b[k], pos = idx_pos[k], cls = idx_cls[k];
+  out[k] = (b >= 0 && b < B && pos >= 0 && pos < Wx && cls >= 0 && cls < C) ? expf(x[((long long)b * Wx + pos) * C + cls]) : 0.f;
 }
 
 
@@ -495,8 +496,8 @@ extern "C" int hwg_segment_weighted_mean_bwd(const float* dout, const float* wgt
 }
 extern "C" int hwg_gather_scores(const float* x, int B, int Wx, int C, const int* idx_b, const int* idx_pos, const int* idx_cls, int n, float* out,
                                  void* stream) {
-  HWG_REQUIRE(x && idx_b && idx_pos && idx_cls && out && n > 0, "gather_scores: bad arguments");
-  hipLaunchKernelGGL(gather_scores_kernel, dim3(hwg_cdiv(n, 128)), dim3(128), 0, (hipStream_t)stream, x, Wx, C, idx_b, idx_pos, idx_cls, n, out);
+  HWG_REQUIRE(x && idx_b && idx_pos && idx_cls && out && B > 0 && Wx > 0 && C > 0 && n > 0, "gather_scores: bad arguments");
+  hipLaunchKernelGGL(gather_scores_kernel, dim3(hwg_cdiv(n, 128)), dim3(128), 0, (hipStream_t)stream, x, B, Wx, C, idx_b, idx_pos, idx_cls, n, out);
   HWG_LAUNCH_CHECK("gather_scores");
   return HWG_OK;
 }
@@ -519,15 +520,16 @@ extern "C" int hwg_linear_bank_bwd(const float* x, const void* dyptr, const void
   HWG_REQUIRE(x && dyptr && wptr && gwptr && O && first_wave && L > 0 && B > 0 && B <= LB_MAXB && I > 0 && halves > 0 && total_outputs > 0,
               "linear_bank_bwd: bad arguments (B <= %d)", LB_MAXB);
   hipStream_t st = (hipStream_t)stream;
+  // (before the first launch: the parameter-gradient kernel ADDS, a call refused afterwards would have changed dW / db already)
+  const size_t need = dx ? hwg_linear_bank_bwd_workspace(total_outputs, B, I) : 0;
+  if (dx && (!workspace || workspace_bytes < need)) {
+    hwg_set_error("linear_bank_bwd: workspace too small (%zu < %zu)", workspace_bytes, need);
+    return HWG_ERR_WORKSPACE;
+  }
   hipLaunchKernelGGL(linear_bank_wgrad_kernel, dim3(hwg_cdiv(total_outputs, 4)), dim3(256), 0, st, x, (const long long*)dyptr, (const long long*)gwptr,
                      (const long long*)gbptr, O, first_wave, L, B, I, halves);
   HWG_LAUNCH_CHECK("linear_bank_wgrad");
   if (dx) {
-    const size_t need = hwg_linear_bank_bwd_workspace(total_outputs, B, I);
-    if (!workspace || workspace_bytes < need) {
-      hwg_set_error("linear_bank_bwd: workspace too small (%zu < %zu)", workspace_bytes, need);
-      return HWG_ERR_WORKSPACE;
-    }
     const int nch = hwg_cdiv(total_outputs, LB_OCHUNK);
     hipLaunchKernelGGL(linear_bank_dgrad_kernel, dim3(nch), dim3(1024), 0, st, (const long long*)dyptr, (const long long*)wptr, O, first_wave, L, B, I, halves,
                        (float*)workspace);

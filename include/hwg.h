@@ -400,20 +400,33 @@ int hwg_argmax_rows(const float* x, int* out, long long rows, int C, void* strea
 /* ------------------------------------------------------------------------------------------
  * Character-specific style extraction helpers (model/char_style.py:204-235,286).
  * ------------------------------------------------------------------------------------------ */
+/* patches[k][j][c] = x[idx_b[k]][idx_pos[k] - window + j][c], j < 2 window + 1; a position outside [0, Wx) reads as 0, and a window whose
+ * CENTRE (idx_b[k], idx_pos[k]) lies outside [0, B) x [0, Wx) is all zeros (also where it reaches back inside): no index is a precondition. */
 int hwg_gather_windows(const float* x, int B, int Wx, int C, const int* idx_b, const int* idx_pos, int n, int window, float* patches, void* stream);
 /* gradient of hwg_gather_windows: dx[b][pos][c] = sum of the window entries that cover (b, pos), gathered in a fixed order (no atomics).
- * At most one window may be centred on a given (sample, column) - true for the arg-max map the windows come from. win_of: B*Wx ints of scratch. */
+ * At most one window may be centred on a given (sample, column) - true for the arg-max map the windows come from. A window whose centre lies
+ * outside [0, B) x [0, Wx) contributes nothing. win_of: B*Wx ints of scratch, written by the call (no more than that, no contents expected). */
 int hwg_scatter_windows(const float* dpatches, int B, int Wx, int C, const int* idx_b, const int* idx_pos, int n, int window, int* win_of,
                         float* dx, void* stream);
+/* out[b][c] = sum_{k: seg[k] == b} wgt[k] v[k][c] / wsum[b] (the plain sum where wsum[b] == 0), wsum[b] = sum of those wgt[k]; a member whose
+ * seg[k] lies outside [0, B) belongs to no line. The backward, dv[k][c] = wgt[k] / wsum[seg[k]] * dout[seg[k]][c], has no B to check against:
+ * PRECONDITION seg[k] in [0, B) for every k, B the line count of the forward call that wrote wsum (it reads wsum[seg[k]] and dout[seg[k]]). */
 int hwg_segment_weighted_mean(const float* v, const float* wgt, const int* seg, int n, int C, int B, float* out, float* wsum, void* stream);
 int hwg_segment_weighted_mean_bwd(const float* dout, const float* wgt, const int* seg, const float* wsum, int n, int C, float* dv, void* stream);
+/* out[k] = exp(x[idx_b[k]][idx_pos[k]][idx_cls[k]]), x [B][Wx][C]; an index outside [0, B) x [0, Wx) x [0, C) gives out[k] = 0 */
 int hwg_gather_scores(const float* x, int B, int Wx, int C, const int* idx_b, const int* idx_pos, const int* idx_cls, int n, float* out, void* stream);
 
 /* Bank of L linear layers that share one input (the generator's ten AdaIN style -> (gamma, beta) affines, pure_gen.py:52-69, in one
  * launch instead of ten): y_l = x W_l^T + b_l, x [B][I] (forward: any B, 16 rows per block; backward: B <= 16), W_l [O_l][I] and b_l [O_l] through device pointer tables.
  * Layer l's outputs are written as `halves` contiguous [B][O_l/halves] blocks starting at y + off[l]; first_wave[L+1] is the
  * running sum of O_l (neuron -> layer map), total_outputs = first_wave[L]. The backward ADDS dW_l / db_l into the tables'
- * buffers and writes dx [B][I] (optional); dyptr[l*halves + h] is the gradient of block h of layer l (0 = unused output). */
+ * buffers and writes dx [B][I] (optional); dyptr[l*halves + h] is the gradient of block h of layer l (0 = unused output).
+ * Null tables and entries. wptr, dyptr and gwptr are tables of L (dyptr: L*halves) entries and must not be null; every wptr[l] must
+ * point to a weight. Forward: bptr == NULL = no layer has a bias; a bptr that is given has L non-null entries. Backward: gwptr[l] == 0 =
+ * the weight of layer l is frozen (its bias still trains through gbptr[l]); gbptr == NULL = no bias trains, gbptr[l] == 0 = that bias is
+ * frozen; a frozen buffer is neither read nor written. dx == NULL = no input gradient: then no workspace is used and workspace may be NULL
+ * with any workspace_bytes. With dx the workspace is checked before anything is launched: a call refused with HWG_ERR_WORKSPACE has
+ * written nothing. */
 int hwg_linear_bank_fwd(const float* x, const void* wptr, const void* bptr, const int* O, const int* first_wave, const void* off, int L, int B,
                         int I, int halves, int total_outputs, float* y, void* stream);
 size_t hwg_linear_bank_bwd_workspace(int total_outputs, int B, int I);
@@ -424,7 +437,10 @@ int hwg_linear_bank_bwd(const float* x, const void* dyptr, const void* wptr, con
 /* Chain of L square Linear(D,D)+LeakyReLU layers (the generator's style-embedding MLP, pure_gen.py:29-38) in one single-workgroup
  * launch per direction: h_{l+1} = lrelu(W_l h_l + b_l, slope). acts [L+1][B][D] receives every h_l (acts[0] = x, acts[L] = output) and is
  * what the backward consumes; the backward ADDS dW_l / db_l into the tables' buffers (null entry = frozen) and writes dx (optional).
- * D = 64 or 128, L <= 8; forward: any B (one workgroup per 8 / 16 rows), backward: B <= 16. */
+ * D = 64 or 128, L <= 8; forward: any B (one workgroup per 8 / 16 rows), backward: B <= 16.
+ * Null tables and entries. wptr and bptr (forward) are tables of L non-null entries: a chain layer always has a bias. Backward: gwptr is a
+ * table of L entries, gwptr[l] == 0 = the weight of layer l is frozen; gbptr == NULL = no bias trains, gbptr[l] == 0 = that bias is
+ * frozen; a frozen buffer is neither read nor written, the data gradient still passes through the layer. dx == NULL = no input gradient. */
 int hwg_mlp_chain_fwd(const float* x, const void* wptr, const void* bptr, int L, int B, int D, float slope, float* acts, void* stream);
 int hwg_mlp_chain_bwd(const float* dout, const float* acts, const void* wptr, const void* gwptr, const void* gbptr, int L, int B, int D,
                       float slope, float* dx, void* stream);
@@ -439,7 +455,10 @@ int hwg_mlp_chain_bwd_split(const float* dout, const float* acts, const void* wp
  * [Cout][Cin][S] and biases; R <= 8; (S, pad) is (1, 0) or (3, 1). Windows are sorted by expert: seg_start[G+1] / seg_eid[G] describe
  * the runs; the rows of a run (windows x R positions) are cut into work tiles of at most 64 rows, tile_seg[t] = run and
  * tile_row0[t] = first row of tile t. Every run is one small GEMM on the matrix cores against its expert's weights.
- * wgrad and segment_accumulate ADD into the buffers addressed by the grad-pointer tables. */
+ * wgrad and segment_accumulate ADD into the buffers addressed by the grad-pointer tables.
+ * Null tables and entries. The tables are indexed by expert id; only the entries of the experts named in seg_eid are read, and those must
+ * not be null (an absent expert's entry may hold anything; its buffers are never touched). bptr == NULL (forward) = no bias is added,
+ * gbptr == NULL (wgrad) = no bias gradient is formed. Forward: Cin % 8 == 0; data gradient: Cout % 4 == 0; wgrad: ntiles >= G. */
 int hwg_grouped_conv1d_fwd(const float* x, const int* seg_start, const int* seg_eid, const int* tile_seg, const int* tile_row0, int ntiles,
                            const void* wptr, const void* bptr, float* y, int R, int Cin, int Cout, int S, int pad, void* stream);
 int hwg_grouped_conv1d_dgrad(const float* dy, const int* seg_start, const int* seg_eid, const int* tile_seg, const int* tile_row0, int ntiles,

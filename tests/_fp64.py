@@ -84,9 +84,16 @@ def ratios(got, want, bound, size=None):
 
 
 def report(entry, shape, ws_bytes, checks):
-    """checks: [(name, got, want float64, bound[, size])] -> prints the case's line, returns what is over its bound"""
+    """checks: [(name, got, want float64, bound[, size])], or (name, ratio) for an error-to-bound ratio the caller formed itself (per-element
+    bounds, yardsticks) -> prints the case's line, returns what is over its bound"""
     parts, bad = [], []
-    for name, got, want, bound, *size in checks:
+    for name, got, *rest in checks:
+        if not rest:
+            parts.append("%s %.2f" % (name, got))
+            if not got <= 1.0:
+                bad.append("%s: %.3g x what it is held to" % (name, got))
+            continue
+        want, bound, *size = rest
         r = ratios(got, want, bound, *size)
         parts.append("%s %.2f/%.2f" % (name, r[0], r[1]))
         if not (r[0] <= 1.0 and r[1] <= 1.0):
